@@ -18,10 +18,17 @@ Multi-GPU: launched by torch.distributed.run, one rank per GPU; z-sticks and
 xy-planes are split evenly over ranks and the pencil <-> slab redistribution
 runs inside the library over one of its data planes: RCCL all-to-all(v) over
 xGMI, IPC peer writes from the stage kernels, or relay routing through idle
-GPUs. Before the timed loop every eligible plane is timed on a few steps
-(config.planes_ms) and the headline runs on the fastest (config.plane_choice;
---plane forces one). The problem size is fixed as N grows (strong scaling);
-`value` is the whole-job rate.
+GPUs. With --full, every eligible plane is timed on a few steps before the
+timed loop (config.planes_ms) and the headline runs on the fastest
+(config.plane_choice); otherwise on the library's default plane (--plane forces
+one). The problem size is fixed as N grows (strong scaling); `value` is the
+whole-job rate.
+
+A plain run sets up, warms up, times --steps steps, writes the last step's
+outputs if --dump-outputs DIR is given, and prints the result line. --full adds
+what takes runs of its own: the round-trip check on every rank
+(config.check_error), the stage profile (config.stage_ms) and, for N > 1, the
+plane probe, the exchange rate and the exchange model.
 """
 from __future__ import annotations
 
@@ -100,15 +107,29 @@ def parse():
                          "measured +2%% over 4 streams at 256^3, profiles/r3/t4_streams.txt), "
                          "per-transform streams on N > 1 GPUs (one transform's all-to-all "
                          "overlaps the others' kernels; distributed plans do not batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the GPU round-trip check on every rank "
+                         "(config.check_error), the per-stage profile of transform 0 "
+                         "(config.stage_ms, --profile-reps), and for N > 1 the data-plane probe "
+                         "(config.planes_ms, --planes-probe), the exchange rate and the exchange "
+                         "model (config.exchange_stats, config.model_ms). A plain run sets up, "
+                         "warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its "
+                         "caller as DIR/<name>.npy: space_<i> (backward) and freq_<i> (forward) "
+                         "of every transform i, complex values as a trailing (re, im) axis, in "
+                         "the run's real dtype; arrays too large for a 48 MiB total are written "
+                         "as a fixed seeded sample of their elements (rank r > 0 of an N > 1 "
+                         "run writes r<r>_<name>.npy)")
     ap.add_argument("--timing", action="store_true", help="print the native timing tree")
     ap.add_argument("--check", action="store_true",
                     help="also compare the backward transform against the dense numpy oracle "
-                         "(1 rank; the GPU round-trip check on every rank always runs)")
+                         "(1 rank; the GPU round-trip check on every rank runs with --full)")
     ap.add_argument("--profile-reps", type=int, default=5,
-                    help="backward+forward pairs of transform 0 timed per stage after the "
+                    help="--full: backward+forward pairs of transform 0 timed per stage after the "
                          "timed loop (0 = no stage profile)")
     ap.add_argument("--planes-probe", type=int, default=1,
-                    help="N > 1: before the timed loop, time a few steps (one transform per step) on "
+                    help="--full, N > 1: before the timed loop, time a few steps (one transform per step) on "
                          "every eligible data plane (rccl / ipc / relay), record them in "
                          "config.planes_ms and run the headline on the fastest (--plane auto)")
     ap.add_argument("--probe-planes", default="rccl,ipc,relay",
@@ -156,6 +177,38 @@ def _roundtrip_gpu(sp, ts, vals, outs, r2c):
         scale = float(base.abs().max().item()) or 1.0
         worst = max(worst, float((o - base).abs().max().item()) / scale)
     return worst
+
+
+DUMP_BYTES = 48 << 20  # all files of one --dump-outputs run together
+DUMP_SEED = 20240607   # of the element sample of an array that does not fit
+
+
+def _dump_outputs(dirname, arrays, share):
+    """Writes every (name, GPU tensor) of `arrays` as dirname/<name>.npy: real values
+    in the tensor's own precision (float32 / float64), a complex tensor as (..., 2)
+    re/im pairs. An array above its part of DUMP_BYTES / share is written as a
+    sample: the sorted first k entries of the DUMP_SEED permutation of its flat
+    element indices, the same elements in every run with the same arguments."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_BYTES // max(1, share) // max(1, len(arrays))
+    picks = {}
+    for name, x in arrays:
+        flat = x.reshape(-1)
+        keep = max(1, budget // flat.element_size())
+        if flat.numel() > keep:
+            key = (flat.numel(), keep)
+            if key not in picks:
+                perm = np.random.default_rng(DUMP_SEED).permutation(flat.numel())[:keep]
+                picks[key] = torch.from_numpy(np.sort(perm)).to(flat.device)
+            flat = flat[picks[key]]
+            host = flat.cpu()
+        else:
+            host = x.cpu()
+        if host.is_complex():
+            host = torch.view_as_real(host)
+        np.save(os.path.join(dirname, name + ".npy"), host.numpy())
 
 
 def _plane_env(name, shared):
@@ -335,12 +388,12 @@ def main():
                                  transform_type=ttype, exchange_type=exch, single=single)
         return setup.grid, setup.transform, setup.indices, setup.z_length
 
-    # N > 1: time every eligible data plane first and run the headline on the
-    # fastest (the library's plane switches are read at grid setup)
+    # N > 1, --full: time every eligible data plane first and run the headline on
+    # the fastest (the library's plane switches are read at grid setup)
     planes_ms, plane_choice = None, None
     if world > 1:
         shared = len(set(_gather_devices(torch, dev, dist, world))) < world
-        if a.planes_probe:
+        if a.full and a.planes_probe:
             planes_ms = _probe_planes(make_transform, dev, cdtype, world, shared, dist,
                                       names=tuple(x for x in a.probe_planes.split(",") if x))
         plane_choice = _choose_plane(a.plane, planes_ms)
@@ -413,22 +466,31 @@ def main():
         if rank == 0:
             print(sp.timing_report(), file=sys.stderr)
         sp.timing_enable(False)
-    # Self-check outside the timed region, on every rank and every transform,
-    # on the GPU: a multi-GPU record carries its own proof that the exchange
-    # moved the right bytes. The worst rank is reported.
-    check = {"roundtrip": _roundtrip_gpu(sp, ts, vals, outs, ttype == sp.TransformType.R2C),
-             "ranks_checked": world, "transforms_checked": T,
-             "method": "max |forward(backward(v)) - v| / max |v| with full scaling, on the GPU"}
-    if dist is not None:
-        e = torch.tensor([check["roundtrip"]], dtype=torch.float64)
-        dist.all_reduce(e, op=dist.ReduceOp.MAX)
-        check["roundtrip"] = float(e.item())
-    check["tolerance"] = 1e-4 if (single or "Float" in a.exchange) else 1e-10
-    check["ok"] = check["roundtrip"] < check["tolerance"]
+    # what the last timed step handed to its caller, before any later pass reuses
+    # the buffers: every transform's space-domain slab and its frequency values
+    if a.dump_outputs:
+        pre = f"r{rank}_" if rank else ""
+        arrays = [(f"{pre}space_{i}", tr.space_domain(sp.ProcessingUnit.GPU)) for i, tr in enumerate(ts)]
+        arrays += [(f"{pre}freq_{i}", o) for i, o in enumerate(outs)]
+        _dump_outputs(a.dump_outputs, arrays, world)
+    # Self-check outside the timed region (--full), on every rank and every
+    # transform, on the GPU: a multi-GPU record carries its own proof that the
+    # exchange moved the right bytes. The worst rank is reported.
+    check = None
+    if a.full:
+        check = {"roundtrip": _roundtrip_gpu(sp, ts, vals, outs, ttype == sp.TransformType.R2C),
+                 "ranks_checked": world, "transforms_checked": T,
+                 "method": "max |forward(backward(v)) - v| / max |v| with full scaling, on the GPU"}
+        if dist is not None:
+            e = torch.tensor([check["roundtrip"]], dtype=torch.float64)
+            dist.all_reduce(e, op=dist.ReduceOp.MAX)
+            check["roundtrip"] = float(e.item())
+        check["tolerance"] = 1e-4 if (single or "Float" in a.exchange) else 1e-10
+        check["ok"] = check["roundtrip"] < check["tolerance"]
     if a.check and world == 1:
-        check.update(_check(a, sp, t, values, gidx, dims, ttype, world))
-    # per-direction stage times of transform 0 alone, and the exchange rate
-    stages = _stage_profile(sp, t, values, out, a.profile_reps) if a.profile_reps > 0 else {}
+        check = dict(check or {}, **_check(a, sp, t, values, gidx, dims, ttype, world))
+    # per-direction stage times of transform 0 alone, and the exchange rate (--full)
+    stages = _stage_profile(sp, t, values, out, a.profile_reps) if a.full and a.profile_reps > 0 else {}
     xstats = None
     if world > 1 and stages:
         eb = (8 if single or "Float" in a.exchange else 16)
@@ -504,6 +566,8 @@ def main():
                 "sync": a.sync,
                 "streams": a.streams if T > 1 else "one",
                 "library_streams": sp.library_streams(),
+                "full": bool(a.full),
+                "outputs_dumped": a.dump_outputs,
                 "check_error": check,
                 "stage_ms": stages,
                 "stage_ms_basis": (f"transform 0 alone, median of {a.profile_reps} backward+forward "

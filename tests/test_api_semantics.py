@@ -365,3 +365,37 @@ def test_bench_plane_choice(monkeypatch):
     assert b._choose_plane("auto", probe)["plane"] == "default"
     assert b._plane_env("relay", True)["SPFFT_RELAY"] == "force"
     assert b._plane_env("relay", False)["SPFFT_RELAY"] == "auto"
+
+
+def test_bench_dump_outputs_files(tmp_path):
+    """bench.py --dump-outputs: one .npy per array in the array's own real precision,
+    complex values as (re, im) pairs; an array above its share of the byte budget is
+    written as the same seeded element sample in every run, and all files together
+    stay below 64 MB."""
+    import importlib.util
+    import os
+    import torch
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(repo, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert b.DUMP_BYTES < 64 * 1000 * 1000
+    g = torch.Generator().manual_seed(5)
+    small = torch.randn(7, 5, dtype=torch.complex128, generator=g)
+    real = torch.randn(3, 4, dtype=torch.float32, generator=g)
+    big = torch.randn(3 * (b.DUMP_BYTES // 16), dtype=torch.complex64, generator=g)
+    arrays = [("small", small), ("real", real), ("big", big), ("empty", small[:0])]
+    b._dump_outputs(str(tmp_path / "a"), arrays, 1)
+    b._dump_outputs(str(tmp_path / "b"), arrays, 1)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n, _ in arrays}
+    assert got["small"].dtype == np.float64 and got["small"].shape == (7, 5, 2)
+    assert np.array_equal(got["small"], torch.view_as_real(small).numpy())
+    assert got["real"].dtype == np.float32 and np.array_equal(got["real"], real.numpy())
+    assert got["empty"].shape == (0, 5, 2)
+    keep = b.DUMP_BYTES // len(arrays) // 8
+    assert got["big"].dtype == np.float32 and got["big"].shape == (keep, 2)
+    pick = np.sort(np.random.default_rng(b.DUMP_SEED).permutation(big.numel())[:keep])
+    assert np.array_equal(got["big"], torch.view_as_real(big).numpy()[pick])
+    assert np.array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= b.DUMP_BYTES + 4096

@@ -1241,3 +1241,41 @@ def test_grid_host_and_gpu(gpu, single):
     fg = tg.forward(torch.as_tensor(space, device="cuda"))
     torch.cuda.synchronize()
     assert max_rel_error(fg.cpu().numpy(), fref) < tol * 10
+
+
+def test_bench_plain_run_dumps_outputs(gpu, tmp_path):
+    """A plain bench.py run times exactly --steps steps and does nothing besides (no
+    round-trip check, no stage profile: they belong to --full), and --dump-outputs
+    writes what the last timed step returned: every transform's space-domain slab
+    (backward of its seeded input, checked against the dense oracle) and its
+    frequency values (the unscaled round trip, N^3 times the input)."""
+    import json
+    import subprocess
+    import sys
+    import torch
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, T = 32, 4
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--size", str(n), "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=repo, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-4000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["dtype"] == "fp64"
+    assert rec["ms_per_step"] > 0 and rec["unit"] == "transforms/s" and rec["higher_is_better"] is True
+    assert abs(rec["value"] - 2 * T * 1e3 / rec["ms_per_step"]) < 1e-6 * rec["value"]
+    cfg = rec["config"]
+    assert cfg["full"] is False and cfg["check_error"] is None and cfg["stage_ms"] == {}
+    assert sorted(os.listdir(tmp_path)) == sorted(f"{k}_{i}.npy" for k in ("space", "freq") for i in range(T))
+    idx = sphere_indices(n, n, n, 0.5)
+    gen = torch.Generator(device=gpu)
+    gen.manual_seed(1234)  # bench.py's input seed of rank 0
+    for i in range(T):
+        v = torch.randn(len(idx), dtype=torch.complex128, device=gpu, generator=gen).cpu().numpy()
+        space = np.load(tmp_path / f"space_{i}.npy")
+        freq = np.load(tmp_path / f"freq_{i}.npy")
+        assert space.dtype == np.float64 and space.shape == (n, n, n, 2)
+        assert freq.dtype == np.float64 and freq.shape == (len(idx), 2)
+        assert max_rel_error(space[..., 0] + 1j * space[..., 1], dense_backward(idx, v, (n, n, n))) < 1e-10
+        assert max_rel_error(freq[:, 0] + 1j * freq[:, 1], v * float(n) ** 3) < 1e-10

@@ -137,7 +137,7 @@ def test_bench_driver_launch_2ranks(gpu):
     # device: JSON contract fields and a checked round trip on every rank
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}",
-           os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
            "--size", "96", "--check"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=300)
@@ -166,7 +166,7 @@ def test_bench_driver_launch_2ranks_rccl(gpu, monkeypatch):
     monkeypatch.setenv("SPFFT_RCCL_VIRTUAL_HOSTS", "1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}",
-           os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
            "--size", "64", "--transforms", "2"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=300)
@@ -202,7 +202,7 @@ def test_bench_rccl_few_hw_queues(gpu, monkeypatch, queues):
     monkeypatch.setenv("SPFFT_EXCH_STICK_BLOCKS", "2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}",
-           os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
+           os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "1",
            "--size", "64", "--transforms", "4", "--streams", "per-transform"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=300)
@@ -302,7 +302,7 @@ def test_bench_ipc_unbuffered_few_hw_queues(gpu, monkeypatch, queues, barrier):
     monkeypatch.setenv("SPFFT_PEER_BARRIER", barrier)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=3",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}",
-           os.path.join(REPO, "bench.py"), "--gpus", "3", "--steps", "4", "--warmup", "1",
+           os.path.join(REPO, "bench.py"), "--full", "--gpus", "3", "--steps", "4", "--warmup", "1",
            "--size", "64", "--transforms", "4", "--streams", "per-transform", "--exchange", "unbuffered"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=300)
@@ -361,7 +361,7 @@ def test_bench_relay_model(gpu, monkeypatch):
     monkeypatch.setenv("SPFFT_RELAY_VIRTUAL", "3")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}",
-           os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
            "--size", "96", "--transforms", "2"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=300)

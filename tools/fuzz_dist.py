@@ -134,6 +134,11 @@ def main():
                   f"planes={plane_dist}{' centred' if centred else ''} err={worst:.2e} {msg}", flush=True)
     if rank == 0:
         print(f"{a.cases - bad}/{a.cases} passed", flush=True)
+    # the last grid's communicator holds the gloo group: drop it on every rank
+    # before the group goes, not while the interpreter unwinds after it
+    grid = t = None
+    gc.collect()
+    dist.barrier()
     dist.destroy_process_group()
     sys.exit(1 if bad else 0)
 

@@ -52,12 +52,12 @@ for s in "$@"; do
     tests:*) step gpu_tests_k 600 $PYT tests -m gpu -q -k "${s#tests:}" ;;
     smoke) step smoke 180 python __graft_entry__.py smoke ;;
     bench)
-      step bench_t4 300 python bench.py --steps 200 --warmup 10
-      step bench_t1 300 python bench.py --steps 200 --warmup 10 --transforms 1 ;;
+      step bench_t4 300 python bench.py --full --steps 200 --warmup 10
+      step bench_t1 300 python bench.py --full --steps 200 --warmup 10 --transforms 1 ;;
     bench32)
-      step bench_c2c256_f32_t1 300 python bench.py --steps 200 --warmup 10 --precision single --transforms 1
-      step bench_c2c256_f32 300 python bench.py --steps 200 --warmup 10 --precision single
-      step bench_r2c512_f32 300 python bench.py --steps 50 --warmup 5 --precision single --type r2c --size 512 ;;
+      step bench_c2c256_f32_t1 300 python bench.py --full --steps 200 --warmup 10 --precision single --transforms 1
+      step bench_c2c256_f32 300 python bench.py --full --steps 200 --warmup 10 --precision single
+      step bench_r2c512_f32 300 python bench.py --full --steps 50 --warmup 5 --precision single --type r2c --size 512 ;;
     prof)
       prof t1 --steps 20 --transforms 1
       prof t4 --steps 20 ;;

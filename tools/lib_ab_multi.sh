@@ -18,7 +18,7 @@ for round in 1 2; do
       port=$((port + 1))
       f="$out/${name}_${np}r_${ex}_t${t}_$round.json"
       timeout -k 10 150 python -m torch.distributed.run --nnodes=1 --nproc-per-node=$np \
-        --master-addr=127.0.0.1 --master-port=$port bench.py --gpus $np --steps 40 --warmup 5 \
+        --master-addr=127.0.0.1 --master-port=$port bench.py --full --gpus $np --steps 40 --warmup 5 \
         --size 256 --exchange $ex --transforms $t --profile-reps 0 > "$f" 2> "${f%.json}.err" \
         || { tail -20 "${f%.json}.err"; exit 1; }
       echo "$name round$round ${np}r $ex T=$t: $(python3 -c 'import json,sys; r=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(round(r["value"],1), r["config"]["data_plane"], r["config"]["check_error"]["ok"])' "$f")"

@@ -9,7 +9,7 @@ for size in 128 256; do
     for mode in stream channel host; do
       port=$((port + 1))
       SPFFT_PEER_BARRIER=$mode timeout -k 10 120 python -m torch.distributed.run --nnodes=1 \
-        --nproc-per-node=2 --master-addr=127.0.0.1 --master-port=$port bench.py --gpus 2 \
+        --nproc-per-node=2 --master-addr=127.0.0.1 --master-port=$port bench.py --full --gpus 2 \
         --steps 20 --warmup 3 --size $size --exchange unbuffered --transforms $T \
         > "$out/bench_${mode}_${size}_t${T}.json" 2> "$out/bench_${mode}_${size}_t${T}.err" || exit 1
       echo "$mode $size T=$T done"

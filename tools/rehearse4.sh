@@ -7,10 +7,10 @@ export TMPDIR=/tmp
 out=${1:-gpurun_out/rehearse}
 mkdir -p "$out"
 SPFFT_RCCL_VIRTUAL_HOSTS=1 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node=4 \
-  --master-addr=127.0.0.1 --master-port=29671 bench.py --gpus 4 --steps 10 --warmup 2 \
+  --master-addr=127.0.0.1 --master-port=29671 bench.py --full --gpus 4 --steps 10 --warmup 2 \
   > "$out/vh4.json" 2> "$out/vh4.err" || { tail -30 "$out/vh4.err"; exit 1; }
 echo "vh4: $(tail -c 2500 "$out/vh4.json")"
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node=2 \
-  --master-addr=127.0.0.1 --master-port=29672 bench.py --gpus 2 --steps 20 --warmup 3 \
+  --master-addr=127.0.0.1 --master-port=29672 bench.py --full --gpus 2 --steps 20 --warmup 3 \
   > "$out/ipc2.json" 2> "$out/ipc2.err" || { tail -30 "$out/ipc2.err"; exit 1; }
 echo "ipc2: $(tail -c 2500 "$out/ipc2.json")"

@@ -10,7 +10,7 @@ run_bench() {  # name nproc size T extra-env...
   local name=$1 np=$2 size=$3 T=$4; shift 4
   port=$((port + 1))
   env "$@" timeout -k 10 150 python -m torch.distributed.run --nnodes=1 --nproc-per-node=$np \
-    --master-addr=127.0.0.1 --master-port=$port bench.py --gpus $np --steps 50 --warmup 5 \
+    --master-addr=127.0.0.1 --master-port=$port bench.py --full --gpus $np --steps 50 --warmup 5 \
     --size $size --transforms $T --exchange unbuffered > "$out/$name.json" 2> "$out/$name.err" \
     || { tail -20 "$out/$name.err"; exit 1; }
   echo "$name: $(python3 -c 'import json,sys; r=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); st=r["config"]["stage_ms"]; print(round(r["value"],1), "transforms/s", round(r["ms_per_step"],3), "ms/step", {d: {k: round(v,3) for k,v in s.items()} for d,s in st.items()})' "$out/$name.json")"

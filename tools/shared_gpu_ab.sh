@@ -16,7 +16,7 @@ for rel in $settings; do
   for ex in unbuffered compact; do
     port=$((port + 1))
     SPFFT_STAGE_RELEASE=$rel timeout -k 10 150 python -m torch.distributed.run --nnodes=1 \
-      --nproc-per-node=2 --master-addr=127.0.0.1 --master-port=$port bench.py --gpus 2 \
+      --nproc-per-node=2 --master-addr=127.0.0.1 --master-port=$port bench.py --full --gpus 2 \
       --steps 20 --warmup 3 --size 256 --exchange $ex --transforms 1 \
       > "$out/rel${rel}_2r256_${ex}.json" 2> "$out/rel${rel}_2r256_${ex}.err" || { tail -20 "$out/rel${rel}_2r256_${ex}.err"; exit 1; }
     echo "rel=$rel 2 ranks 256^3 $ex: $(python3 -c 'import json,sys; r=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(round(r["value"],1), "transforms/s", r["config"]["check_error"]["roundtrip"], r["config"]["data_plane"])' "$out/rel${rel}_2r256_${ex}.json")"
