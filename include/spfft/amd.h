@@ -137,6 +137,36 @@ SPFFT_EXPORT SpfftError spfft_amd_float_transform_backward_exchange(SpfftFloatTr
 SPFFT_EXPORT SpfftError spfft_amd_float_transform_backward_xy(SpfftFloatTransform t,
                                                               SpfftProcessingUnitType outputLocation);
 
+/* Local operator: output = forward(V * backward(input)) in one call, with the
+ * real potential V over the local space domain [localZ][dimY][dimX] (double or
+ * float as the transform). input, potential and output are host or device
+ * pointers (device pointers are used in place, as backward does for its input);
+ * input == output is allowed. After the call the contents of the space domain
+ * are unspecified: fused plans (C2C transforms whose x lines fit one workgroup)
+ * never form it and leave it untouched, other plans (R2C, long x lines) pass
+ * through it. A null potential is SPFFT_INVALID_PARAMETER_ERROR. */
+SPFFT_EXPORT SpfftError spfft_amd_transform_apply_local(SpfftTransform t, const double* input,
+                                                        const double* potential, double* output,
+                                                        SpfftScalingType scaling);
+SPFFT_EXPORT SpfftError spfft_amd_float_transform_apply_local(SpfftFloatTransform t,
+                                                              const float* input,
+                                                              const float* potential, float* output,
+                                                              SpfftScalingType scaling);
+/* *fused = 1 if the plan runs the fused x apply stage on the GPU, else 0. */
+SPFFT_EXPORT SpfftError spfft_amd_transform_apply_local_fused(SpfftTransform t, int* fused);
+SPFFT_EXPORT SpfftError spfft_amd_float_transform_apply_local_fused(SpfftFloatTransform t,
+                                                                    int* fused);
+/* apply_local of n transforms (distinct grids) with their phases interleaved;
+ * identical fused plans on one GPU share one launch per stage (SPFFT_BATCH). */
+SPFFT_EXPORT SpfftError spfft_amd_multi_transform_apply_local(int n, SpfftTransform* transforms,
+                                                              const double* const* inputs,
+                                                              const double* const* potentials,
+                                                              double* const* outputs,
+                                                              const SpfftScalingType* scalings);
+SPFFT_EXPORT SpfftError spfft_amd_float_multi_transform_apply_local(
+    int n, SpfftFloatTransform* transforms, const float* const* inputs,
+    const float* const* potentials, float* const* outputs, const SpfftScalingType* scalings);
+
 /* Timer tree (SPFFT_TIMING=1 or spfft_amd_timing_enable). enable: 0 off, 1 host
  * scopes only (like the reference's timer), 2 host scopes and GPU stage times
  * (a hipEvent per stage boundary, nodes gpu/<direction>/<stage>). */

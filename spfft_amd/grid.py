@@ -91,6 +91,26 @@ def _data_ptr(a, prec: _Precision, writable: bool, what: str):
     return arr.ctypes.data, arr
 
 
+def _potential_ptr(v, prec: _Precision, shape):
+    """Returns (address, keepalive) of a real potential of the space domain's shape."""
+    if v is None:
+        return None, None
+    if _is_torch(v):
+        if v.dtype != prec.torch_real:
+            raise TypeError(f"potential: expected {prec.torch_real}, got {v.dtype}")
+        if tuple(v.shape) != tuple(shape):
+            raise ValueError(f"potential: expected shape {tuple(shape)}, got {tuple(v.shape)}")
+        v = v.contiguous()
+        return v.data_ptr(), v
+    arr = np.asarray(v)
+    if arr.dtype != prec.real:
+        raise TypeError(f"potential: expected {np.dtype(prec.real)}, got {arr.dtype}")
+    if tuple(arr.shape) != tuple(shape):
+        raise ValueError(f"potential: expected shape {tuple(shape)}, got {tuple(arr.shape)}")
+    arr = np.ascontiguousarray(arr)
+    return arr.ctypes.data, arr
+
+
 class _GridBase:
     _single = False
 
@@ -350,6 +370,34 @@ class _TransformBase:
         del keep
         return output
 
+    def apply_local(self, values, potential, output=None, scaling=Scaling.NONE):
+        """Local operator in one call: forward(potential * backward(values)).
+
+        `potential` is a real array (numpy or torch, host or device memory) of shape
+        space_domain_shape() and the transform's precision. `output` may be `values`.
+        The contents of the space domain are unspecified afterwards; fused plans
+        (see apply_local_fused) never form it and leave it untouched. Returns the
+        frequency values."""
+        vptr, vkeep = _potential_ptr(potential, self._prec, self.space_domain_shape())
+        iptr, ikeep = _data_ptr(values, self._prec, False, "values")
+        if output is None:
+            output = self._default_output()
+        optr, okeep = _data_ptr(output, self._prec, True, "output")
+        _check(self._prec.amd_fn("transform_apply_local")(self._h, iptr, vptr, optr, int(scaling)))
+        # asynchronous execution (set_stream(..., synchronous=False)) may still read them
+        self._step_keep = (ikeep, vkeep, okeep)
+        return output
+
+    @property
+    def apply_local_fused(self) -> bool:
+        """True if apply_local runs the fused x stage (GPU, C2C, x lines of one workgroup)."""
+        c = self._cache.get("apply_local_fused")
+        if c is None:
+            v = ctypes.c_int()
+            _check(self._prec.amd_fn("transform_apply_local_fused")(self._h, ctypes.byref(v)))
+            c = self._cache["apply_local_fused"] = bool(v.value)
+        return c
+
     # --------------------------------------------------- streams / step API
     def set_stream(self, stream=None, synchronous: bool = True):
         """Execute on a HIP stream (int handle or torch.cuda.Stream; 0 = legacy default
@@ -463,4 +511,30 @@ def multi_transform_forward(transforms, outputs=None, input_locations=None, scal
     locs = (ctypes.c_int * max(1, n))(*[int(x) for x in input_locations])
     scs = (ctypes.c_int * max(1, n))(*[int(x) for x in scalings])
     _check(prec.fn("multi_transform_forward")(n, arr, locs, ptrs, scs))
+    return outputs
+
+
+def multi_transform_apply_local(transforms, inputs, potentials, outputs=None, scalings=None):
+    """apply_local of several independent transforms (distinct grids), overlapped;
+    identical fused plans on one GPU share one launch per stage."""
+    n, prec, arr = _multi(transforms)
+    if len(inputs) != n or len(potentials) != n:
+        raise ValueError("one input and one potential per transform")
+    if scalings is None:
+        scalings = [Scaling.NONE] * n
+    if outputs is None:
+        outputs = [t._default_output() for t in transforms]
+    keeps = []
+    iptrs, vptrs, optrs = ((ctypes.c_void_p * max(1, n))() for _ in range(3))
+    for i, t in enumerate(transforms):
+        vptrs[i], k = _potential_ptr(potentials[i], prec, t.space_domain_shape())
+        keeps.append(k)
+        iptrs[i], k = _data_ptr(inputs[i], prec, False, "values")
+        keeps.append(k)
+        optrs[i], k = _data_ptr(outputs[i], prec, True, "output")
+        keeps.append(k)
+    scs = (ctypes.c_int * max(1, n))(*[int(x) for x in scalings])
+    _check(prec.amd_fn("multi_transform_apply_local")(n, arr, iptrs, vptrs, optrs, scs))
+    for t in transforms:
+        t._step_keep = keeps
     return outputs

@@ -91,15 +91,31 @@ class PlaneWaveModel:
         self.transforms = [t0] + [t0.clone() for _ in range(max(1, num_transforms) - 1)]
         self.volume_points = n0 * n1 * n2
 
-    def apply_local_potential(self, psi: Sequence, v_r) -> List:
+    def apply_local_potential(self, psi: Sequence, v_r, unfused: bool = False) -> List:
         """H_loc psi_b for every band b: FFT^-1[V(r) FFT[psi_b](r)] (band coefficients in,
-        band coefficients out). `v_r` is the real-space potential [z][y][x]."""
-        from ..grid import multi_transform_backward, multi_transform_forward
+        band coefficients out). `v_r` is the real-space potential [z][y][x].
+
+        One multi_transform_apply_local call per group of bands (on the GPU the x
+        stage multiplies by V(r) in LDS and the space domain is never formed);
+        `unfused` runs the composition backward, V(r) multiply, forward instead."""
+        from ..grid import (multi_transform_apply_local, multi_transform_backward,
+                            multi_transform_forward)
         out = []
         T = len(self.transforms)
+        if not unfused:
+            # the potential in the transforms' precision, where the transforms run
+            real = self.transforms[0]._prec
+            if hasattr(v_r, "mul_"):
+                v = v_r.to(real.torch_real).contiguous()
+            else:
+                v = np.ascontiguousarray(v_r, dtype=real.real)
         for start in range(0, len(psi), T):
             group = list(psi[start:start + T])
             ts = self.transforms[:len(group)]
+            if not unfused:
+                out.extend(multi_transform_apply_local(ts, group, [v] * len(ts),
+                                                       scalings=[Scaling.FULL] * len(ts)))
+                continue
             spaces = multi_transform_backward(ts, group)
             for s in spaces:
                 if hasattr(s, "mul_"):

@@ -118,6 +118,11 @@ def _prototypes(lib):
     sig["spfft_amd_float_transform_backward_z"] = [V, D]
     sig["spfft_amd_float_transform_backward_exchange"] = [V, I]
     sig["spfft_amd_float_transform_backward_xy"] = [V, I]
+    for pre in ("spfft_amd_", "spfft_amd_float_"):
+        sig[pre + "transform_apply_local"] = [V, D, D, D, I]
+        sig[pre + "transform_apply_local_fused"] = [V, c_int_p]
+        sig[pre + "multi_transform_apply_local"] = [I, c_void_pp, c_void_pp, c_void_pp, c_void_pp,
+                                                    c_int_p]
     sig["spfft_amd_timing_enable"] = [I]
     sig["spfft_amd_timing_reset"] = []
     sig["spfft_amd_timing_json"] = [ctypes.c_char_p, ctypes.c_size_t, c_size_t_p]

@@ -33,6 +33,12 @@ void multi_backward_handles(int n, Transform** ts, double** in, SpfftProcessingU
 void multi_forward_handles(int n, TransformFloat** ts, SpfftProcessingUnitType* in, float** out,
                            SpfftScalingType* sc);
 void multi_backward_handles(int n, TransformFloat** ts, float** in, SpfftProcessingUnitType* out);
+void multi_apply_local_handles(int n, Transform** ts, const double* const* in,
+                               const double* const* pot, double* const* out,
+                               const SpfftScalingType* sc);
+void multi_apply_local_handles(int n, TransformFloat** ts, const float* const* in,
+                               const float* const* pot, float* const* out,
+                               const SpfftScalingType* sc);
 }  // namespace spfft
 
 using namespace spfft;
@@ -499,6 +505,55 @@ SpfftError spfft_amd_float_transform_backward_exchange(SpfftFloatTransform t, in
 }
 SpfftError spfft_amd_float_transform_backward_xy(SpfftFloatTransform t, SpfftProcessingUnitType loc) {
   return with_handle<TransformFloat>(t, [&](TransformFloat& x) { x.backward_xy(loc); });
+}
+
+SpfftError spfft_amd_transform_apply_local(SpfftTransform t, const double* input,
+                                           const double* potential, double* output,
+                                           SpfftScalingType scaling) {
+  return with_handle<Transform>(
+      t, [&](Transform& x) { x.impl()->apply_local(input, potential, output, scaling); });
+}
+SpfftError spfft_amd_float_transform_apply_local(SpfftFloatTransform t, const float* input,
+                                                 const float* potential, float* output,
+                                                 SpfftScalingType scaling) {
+  return with_handle<TransformFloat>(
+      t, [&](TransformFloat& x) { x.impl()->apply_local(input, potential, output, scaling); });
+}
+SpfftError spfft_amd_transform_apply_local_fused(SpfftTransform t, int* fused) {
+  if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
+  return with_handle<Transform>(
+      t, [&](Transform& x) { *fused = x.impl()->apply_local_fused() ? 1 : 0; });
+}
+SpfftError spfft_amd_float_transform_apply_local_fused(SpfftFloatTransform t, int* fused) {
+  if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
+  return with_handle<TransformFloat>(
+      t, [&](TransformFloat& x) { *fused = x.impl()->apply_local_fused() ? 1 : 0; });
+}
+SpfftError spfft_amd_multi_transform_apply_local(int n, SpfftTransform* transforms,
+                                                 const double* const* inputs,
+                                                 const double* const* potentials,
+                                                 double* const* outputs,
+                                                 const SpfftScalingType* scalings) {
+  if (n > 0 && !transforms) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < n; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_apply_local_handles(n, reinterpret_cast<Transform**>(transforms), inputs, potentials,
+                              outputs, scalings);
+  });
+}
+SpfftError spfft_amd_float_multi_transform_apply_local(int n, SpfftFloatTransform* transforms,
+                                                       const float* const* inputs,
+                                                       const float* const* potentials,
+                                                       float* const* outputs,
+                                                       const SpfftScalingType* scalings) {
+  if (n > 0 && !transforms) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < n; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_apply_local_handles(n, reinterpret_cast<TransformFloat**>(transforms), inputs, potentials,
+                              outputs, scalings);
+  });
 }
 
 SpfftError spfft_amd_timing_enable(int enable) {

@@ -147,6 +147,69 @@ void multi_backward(const std::vector<TransformImpl<T>*>& ts, const T* const* in
     if (ts[i]->is_gpu() && ts[i]->gpu()->synchronous()) ts[i]->synchronize();
 }
 
+// apply_local of every transform, phases interleaved like the directions above:
+// fused GPU plans with equal keys share one launch per stage.
+template <typename T>
+void multi_apply_local(const std::vector<TransformImpl<T>*>& ts, const T* const* inputs,
+                       const T* const* potentials, T* const* outputs,
+                       const SpfftScalingType* scalings) {
+  SPFFT_TIMED_SCOPE("multi_apply_local");
+  check_distinct_grids(ts);
+  const int n = static_cast<int>(ts.size());
+  if (n > 0 && (!inputs || !potentials || !outputs || !scalings)) throw InvalidParameterError();
+  for (int i = 0; i < n; ++i) {
+    if (scalings[i] != SPFFT_NO_SCALING && scalings[i] != SPFFT_FULL_SCALING)
+      throw InvalidParameterError();
+    if (!potentials[i]) throw InvalidParameterError();
+  }
+  const std::vector<bool> batched = run_batches<T>(
+      ts,
+      [&](int i) {
+        return ts[i]->apply_local_fused() && is_device_pointer(potentials[i]) &&
+               (ts[i]->plan().numLocalElements == 0 ||
+                (is_device_pointer(inputs[i]) && is_device_pointer(outputs[i])));
+      },
+      [&](int i) { return static_cast<int>(scalings[i]); },
+      [&](const std::vector<int>& g) {
+        std::vector<GpuExecutor<T>*> ex;
+        std::vector<const T*> ins, pots;
+        std::vector<T*> outs;
+        for (int j : g) {
+          ex.push_back(ts[j]->gpu());
+          ins.push_back(inputs[j]);
+          pots.push_back(potentials[j]);
+          outs.push_back(outputs[j]);
+        }
+        GpuExecutor<T>::apply_local_batch(ex, ins, pots, outs, scalings[g[0]]);
+      });
+  for (int i = 0; i < n; ++i)
+    if (ts[i]->is_gpu() && !batched[i]) ts[i]->backward_z(inputs[i]);
+  for (int i = 0; i < n; ++i)
+    if (!ts[i]->is_gpu()) {
+      ts[i]->backward_z(inputs[i]);
+      ts[i]->backward_exchange(true);
+    }
+  for (int i = 0; i < n; ++i)
+    if (ts[i]->is_gpu() && !batched[i]) {
+      ts[i]->backward_exchange(true);
+      ts[i]->apply_local_xy(potentials[i]);
+    }
+  for (int i = 0; i < n; ++i)
+    if (!ts[i]->is_gpu()) {
+      ts[i]->apply_local_xy(potentials[i]);
+      ts[i]->forward_exchange(true);
+    }
+  for (int i = 0; i < n; ++i)
+    if (ts[i]->is_gpu() && !batched[i]) {
+      ts[i]->forward_exchange(true);
+      ts[i]->forward_z(outputs[i], scalings[i]);
+    }
+  for (int i = 0; i < n; ++i)
+    if (!ts[i]->is_gpu()) ts[i]->forward_z(outputs[i], scalings[i]);
+  for (int i = 0; i < n; ++i)
+    if (ts[i]->is_gpu() && ts[i]->gpu()->synchronous()) ts[i]->synchronize();
+}
+
 template <typename TR, typename T>
 std::vector<TransformImpl<T>*> impls(int n, TR* transforms) {
   if (n < 0 || (n > 0 && !transforms)) throw InvalidParameterError();
@@ -194,6 +257,22 @@ void multi_backward_handles(int n, Transform** ts, double** in, SpfftProcessingU
   std::vector<TransformImpl<double>*> v;
   for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
   multi_backward<double>(v, in, out);
+}
+void multi_apply_local_handles(int n, Transform** ts, const double* const* in,
+                               const double* const* pot, double* const* out,
+                               const SpfftScalingType* sc) {
+  if (n < 0 || (n > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<double>*> v;
+  for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_apply_local<double>(v, in, pot, out, sc);
+}
+void multi_apply_local_handles(int n, TransformFloat** ts, const float* const* in,
+                               const float* const* pot, float* const* out,
+                               const SpfftScalingType* sc) {
+  if (n < 0 || (n > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<float>*> v;
+  for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_apply_local<float>(v, in, pot, out, sc);
 }
 void multi_forward_handles(int n, TransformFloat** ts, SpfftProcessingUnitType* in, float** out,
                            SpfftScalingType* sc) {

@@ -100,6 +100,43 @@ void TransformImpl<T>::backward(const T* input, SpfftProcessingUnitType outputLo
 }
 
 template <typename T>
+void TransformImpl<T>::apply_local(const T* input, const T* potential, T* output,
+                                   SpfftScalingType scaling) {
+  SPFFT_TIMED_SCOPE("apply_local");
+  if (scaling != SPFFT_NO_SCALING && scaling != SPFFT_FULL_SCALING) throw InvalidParameterError();
+  if (!potential) throw InvalidParameterError();
+  backward_z(input);
+  backward_exchange(false);
+  apply_local_xy(potential);
+  forward_exchange(false);
+  forward_z(output, scaling);
+  if (gpu_ && gpu_->synchronous()) gpu_->synchronize();
+}
+
+template <typename T>
+void TransformImpl<T>::apply_local_xy(const T* potential) {
+  if (!potential) throw InvalidParameterError();
+  if (gpu_) {
+    gpu_->apply_local_xy(potential);
+    return;
+  }
+  // host: the plain composition through the space domain
+  host_->backward_xy();
+  const IndexPlan& p = *plan_;
+  const std::size_t count = static_cast<std::size_t>(p.local_planes()) * p.dimY * p.dimX;
+  T* space = host_->space_domain();
+  if (p.type == SPFFT_TRANS_R2C) {
+    for (std::size_t i = 0; i < count; ++i) space[i] *= potential[i];
+  } else {
+    for (std::size_t i = 0; i < count; ++i) {
+      space[2 * i] *= potential[i];
+      space[2 * i + 1] *= potential[i];
+    }
+  }
+  host_->forward_xy();
+}
+
+template <typename T>
 void TransformImpl<T>::forward_xy(SpfftProcessingUnitType inputLocation) {
   if (host_) {
     if (inputLocation != SPFFT_PU_HOST) throw InvalidParameterError();

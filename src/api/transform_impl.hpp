@@ -24,6 +24,14 @@ public:
   void forward(SpfftProcessingUnitType inputLocation, T* output, SpfftScalingType scaling);
   void backward(const T* input, SpfftProcessingUnitType outputLocation);
 
+  // output = forward(V * backward(input)) with the real potential V over the
+  // local space domain [localZ][dimY][dimX]; the space domain's contents are
+  // unspecified afterwards (untouched on the fused GPU path)
+  void apply_local(const T* input, const T* potential, T* output, SpfftScalingType scaling);
+  bool apply_local_fused() const { return gpu_ && gpu_->apply_local_fused(); }
+  // the stage between the two exchanges of apply_local (multi-transform interleaving)
+  void apply_local_xy(const T* potential);
+
   void forward_xy(SpfftProcessingUnitType inputLocation);
   void forward_exchange(bool nonBlocking);
   void forward_z(T* output, SpfftScalingType scaling);

@@ -65,6 +65,9 @@ GpuExecutor<T>::GpuExecutor(std::shared_ptr<GridImpl<T>> grid,
     interPlanes_ = perPlane > 0 ? static_cast<int>(std::min<long long>(L, std::max(1LL, cap / perPlane))) : L;
   }
   setup_long_axes();
+  // apply_local runs the fused x apply stage for C2C transforms whose x lines
+  // fit one workgroup; R2C (packed-real pair) and long x lines run unfused
+  applyFused_ = p.type == SPFFT_TRANS_C2C && !longX_;
   // Backward z -> y hand-off through the Infinity Cache: a single rank's z
   // stage writes the stick array that its y stage reads next. With the default
   // cache policy on both sides (instead of streaming) and a stick array that
@@ -219,7 +222,7 @@ void GpuExecutor<T>::log_plan() const {
   if (p.size > 1) plane = const_cast<GridImpl<T>&>(*grid_).device_comm().describe();
   std::fprintf(stderr,
                "spfft[gpu rank %d/%d] %dx%dx%d %s %s: sticks=%d planes=%d columns=%d | z{%s} "
-               "y{%s} x{%s}%s inter_planes=%d | exchange=%s%s plane=%s chunks=%d stick_blocks=%d "
+               "y{%s} x{%s}%s inter_planes=%d apply_local=%s | exchange=%s%s plane=%s chunks=%d stick_blocks=%d "
                "steps=%zu+%zu (%.2f MB per peer) peer_writes=%d peer_offsets=[%lld, %lld] "
                "library_streams=%d\n",
                p.rank, p.size, p.dimX, p.dimY, p.dimZ,
@@ -227,7 +230,8 @@ void GpuExecutor<T>::log_plan() const {
                p.local_planes(), p.num_columns(),
                describe(longZ_, lpZ_, p.dimZ, false).c_str(), describe(longY_, lpY_, p.dimY, true).c_str(),
                describe(longX_, lpX_, twXh_ ? p.dimX / 2 : p.dimX, true).c_str(),
-               twXh_ ? " packed-real" : "", interPlanes_, layout_.buffered ? "buffered" : "compact",
+               twXh_ ? " packed-real" : "", interPlanes_, applyFused_ ? "fused" : "unfused",
+               layout_.buffered ? "buffered" : "compact",
                floatExchange_ ? "-float" : "", plane.c_str(), exchChunks_, stickBlocks_, bwdSteps_.size(),
                fwdSteps_.size(), chunkModel_ / 1e6, peerWrites_ ? 1 : 0, peerOffsetRange_[0],
                peerOffsetRange_[1], GpuStream::live());
@@ -1283,6 +1287,87 @@ void GpuExecutor<T>::forward_z(T* output, SpfftScalingType scaling) {
   }
 }
 
+// -------------------------------------------------------------- local operator
+// apply_local = backward_z, backward_exchange, apply_local_xy, forward_exchange,
+// forward_z (TransformImpl::apply_local). Fused plans (C2C, x lines of one
+// workgroup) never form the space domain: per plane range of the intermediate
+// y backward, x apply (inverse x FFT, V multiply, forward x FFT in LDS, in
+// place) and y forward. The y forward stage writes the slab-side elements of
+// the planes its range's y backward stage has just read, so plane ranges and
+// exchange chunks run through unchanged. Other plans compose the existing
+// stages around an in-place multiply of the space domain.
+template <typename T>
+const T* GpuExecutor<T>::device_potential(const T* potential) {
+  const IndexPlan& p = *plan_;
+  const std::size_t count = static_cast<std::size_t>(p.local_planes()) * p.dimY * p.dimX;
+  if (count == 0) return potential;
+  if (!potential) throw InvalidParameterError();
+  if (is_device_pointer(potential)) return potential;
+  if (!potential_ || potential_->bytes() < count * sizeof(T))
+    potential_.reset(new DeviceBuffer(count * sizeof(T)));
+  gpu_check(hipMemcpyAsync(potential_->data<T>(), potential, count * sizeof(T), hipMemcpyHostToDevice,
+                           stream_),
+            "hipMemcpyAsync");
+  return potential_->data<T>();
+}
+
+template <typename T>
+void GpuExecutor<T>::apply_local_xy(const T* potential) {
+  SPFFT_TIMED_SCOPE("gpu_apply_local_xy");
+  DeviceGuard guard(deviceId_);
+  const IndexPlan& p = *plan_;
+  const T* pot = device_potential(potential);
+  if (!applyFused_) {
+    backward_xy(SPFFT_PU_GPU);
+    dev::launch_space_scale<T>(grid_->device_slot(GridImpl<T>::kSpace), pot,
+                               static_cast<long long>(p.local_planes()) * p.dimY * p.dimX,
+                               p.type == SPFFT_TRANS_R2C, stream_);
+    stage_mark("backward", "multiply");
+    forward_xy(SPFFT_PU_GPU);
+    return;
+  }
+  const bool pipe = pipelined();
+  {
+    StageEnd stageEnd{this, "backward", pipe ? "exchange+y+x_apply+y" : "y+x_apply+y"};
+    void* slab = grid_->device_slot(GridImpl<T>::kSlabSide);
+    auto* inter = static_cast<cx<T>*>(grid_->device_slot(GridImpl<T>::kInter));
+    if (peerWrites_) {
+      grid_->device_comm().note_read(GridImpl<T>::kSlabSide);
+      // the y forward stage stores straight into the peers' stick sides
+      grid_->device_comm().prepare_write(GridImpl<T>::kStickSide, stream_);
+    }
+    const int K = pipe ? exchChunks_ : 1;
+    for (int k = 0; k < K; ++k) {
+      if (pipe) chunkEv_[k]->wait_on(stream_);  // chunk k has arrived
+      const int zb = pipe ? planeBounds_[k] : 0;
+      const int ze = pipe ? planeBounds_[k + 1] : p.local_planes();
+      for (int z0 = zb; z0 < ze; z0 += interPlanes_) {
+        auto yb = yargs();
+        auto xa = xargs();
+        yb.zBegin = xa.zBegin = z0;
+        yb.L = xa.L = std::min(ze, z0 + interPlanes_);
+        auto yf = yb;
+        if (pipe) {
+          yb.colBase = colBaseChunk_[k] ? colBaseChunk_[k]->data<long long>() : nullptr;
+          set_col_desc(yb, colDescChunk_[k]);
+          yf = yb;
+        } else if (peerWrites_) {
+          yf.colBase = colBaseRemote_ ? colBaseRemote_->data<long long>() : nullptr;
+          set_col_desc(yf, colDescRemote_);
+        }
+        yb.plainSticks = plainHandoff_;
+        cx<T>* tile = inter_for(inter, z0);
+        y_backward_launch(yb, slab, tile);
+        dev::launch_x_apply<T>(xa, pot, tile, false, twX_->data<cx<T>>(), stream_);
+        y_forward_launch(yf, tile, slab);
+      }
+      if (pipe) chunkEv_[k]->record(stream_);  // chunk k may leave
+    }
+  }
+  // the forward exchange and z stage follow: their marks belong to "forward"
+  stage_mark("forward", nullptr);
+}
+
 // ------------------------------------------------------- batched multi-transform
 namespace {
 struct Fnv {
@@ -1464,6 +1549,80 @@ void GpuExecutor<T>::forward_batch(const std::vector<GpuExecutor*>& ex, const st
                                   static_cast<cx<T>*>(yb.out[0]), l->twY_->data<cx<T>>(), s);
   dev::launch_z_forward<T, cx<T>>(za, static_cast<const cx<T>*>(zb.in[0]),
                                   static_cast<cx<T>*>(zb.out[0]), factor, l->twZ_->data<cx<T>>(), s);
+  batch_release(ex);
+}
+
+// One launch per stage for a batch of fused plans: z backward, y backward,
+// x apply, y forward, z forward. A potential shared by the whole batch is read
+// with the default cache policy (the later members find it in the caches).
+template <typename T>
+void GpuExecutor<T>::apply_local_batch(const std::vector<GpuExecutor*>& ex,
+                                       const std::vector<const T*>& inputs,
+                                       const std::vector<const T*>& potentials,
+                                       const std::vector<T*>& outputs, SpfftScalingType scaling) {
+  SPFFT_TIMED_SCOPE("gpu_apply_local_batch");
+  const int n = static_cast<int>(ex.size());
+  if (n < 1 || n > dev::kMaxBatch || inputs.size() != ex.size() || potentials.size() != ex.size() ||
+      outputs.size() != ex.size())
+    throw InternalError();
+  GpuExecutor* l = ex[0];
+  DeviceGuard guard(l->deviceId_);
+  for (GpuExecutor* e : ex)
+    if (!e->batchable() || !e->applyFused_ || e->batchKey_ != l->batchKey_) throw InternalError();
+  batch_join(ex);
+  const IndexPlan& p = *l->plan_;
+  const T factor = scaling == SPFFT_FULL_SCALING
+                       ? static_cast<T>(1.0 / (static_cast<double>(p.dimX) * p.dimY * p.dimZ))
+                       : T(1);
+  dev::BatchPtrs zb{}, yb{}, xb{}, yf{}, zf{};
+  zb.count = yb.count = xb.count = yf.count = zf.count = n;
+  bool shared = true;
+  for (int i = 0; i < n; ++i) {
+    GpuExecutor* e = ex[i];
+    if (p.numLocalElements > 0 && (!inputs[i] || !is_device_pointer(inputs[i]) || !outputs[i] ||
+                                   !is_device_pointer(outputs[i])))
+      throw InvalidParameterError();
+    if (p.local_planes() > 0 && (!potentials[i] || !is_device_pointer(potentials[i])))
+      throw InvalidParameterError();
+    shared = shared && potentials[i] == potentials[0];
+    void* stick = e->grid_->device_slot(GridImpl<T>::kStickSide);
+    void* slab = e->grid_->device_slot(GridImpl<T>::kSlabSide);
+    void* inter = e->grid_->device_slot(GridImpl<T>::kInter);
+    zb.in[i] = inputs[i];
+    zb.out[i] = stick;
+    yb.in[i] = slab;
+    yb.out[i] = inter;
+    xb.in[i] = potentials[i];
+    xb.out[i] = inter;
+    yf.in[i] = inter;
+    yf.out[i] = slab;
+    zf.in[i] = stick;
+    zf.out[i] = outputs[i];
+  }
+  auto za = l->zargs();
+  auto ya = l->yargs();
+  auto xa = l->xargs();
+  hipStream_t s = l->stream_;
+  za.batch = zb;
+  dev::launch_z_backward<T, cx<T>>(za, static_cast<const cx<T>*>(zb.in[0]),
+                                   static_cast<cx<T>*>(zb.out[0]), l->twZ_->data<cx<T>>(), s);
+  ya.batch = yb;
+  dev::launch_y_backward<T, cx<T>>(ya, static_cast<const cx<T>*>(yb.in[0]),
+                                   static_cast<cx<T>*>(yb.out[0]), l->twY_->data<cx<T>>(), s);
+  xa.batch = xb;
+  {
+    // (the scope names the kernel variant: plain loads of a shared potential measured
+    // +1% against streaming ones at 256^3, 8 bands per call; profiles/r7/apply_local)
+    SPFFT_TIMED_SCOPE(shared ? "x_apply_shared_potential" : "x_apply_streamed_potential");
+    dev::launch_x_apply<T>(xa, static_cast<const T*>(xb.in[0]), static_cast<cx<T>*>(xb.out[0]), shared,
+                           l->twX_->data<cx<T>>(), s);
+  }
+  ya.batch = yf;
+  dev::launch_y_forward<T, cx<T>>(ya, static_cast<const cx<T>*>(yf.in[0]),
+                                  static_cast<cx<T>*>(yf.out[0]), l->twY_->data<cx<T>>(), s);
+  za.batch = zf;
+  dev::launch_z_forward<T, cx<T>>(za, static_cast<const cx<T>*>(zf.in[0]),
+                                  static_cast<cx<T>*>(zf.out[0]), factor, l->twZ_->data<cx<T>>(), s);
   batch_release(ex);
 }
 

@@ -60,6 +60,20 @@ public:
   static void forward_batch(const std::vector<GpuExecutor*>& ex, const std::vector<T*>& outputs,
                             SpfftScalingType scaling);
 
+  // Local-operator application (TransformImpl::apply_local): the stage between
+  // backward_exchange and forward_exchange. Fused plans run y backward, the x
+  // apply stage (inverse x FFT, multiply by the real potential [localZ][Y][X],
+  // forward x FFT, in LDS) and y forward per plane range and leave the space
+  // domain untouched; other plans (R2C, long x lines) run backward_xy, an
+  // in-place multiply of the space domain and forward_xy. `potential` is a
+  // host or device pointer.
+  void apply_local_xy(const T* potential);
+  bool apply_local_fused() const { return applyFused_; }
+  // batchable() fused plans with equal keys: one launch per stage (device pointers)
+  static void apply_local_batch(const std::vector<GpuExecutor*>& ex, const std::vector<const T*>& inputs,
+                                const std::vector<const T*>& potentials, const std::vector<T*>& outputs,
+                                SpfftScalingType scaling);
+
   void synchronize();
   bool synchronous() const { return synchronous_; }
   // Execute on `stream` (nullptr = the legacy default stream); work is then
@@ -92,6 +106,9 @@ private:
   dev::YArgs yargs() const;
   dev::XArgs xargs() const;
   cx<T>* staging(std::size_t elems);
+  const T* device_potential(const T* potential);  // stages a host potential
+  std::unique_ptr<DeviceBuffer> potential_;
+  bool applyFused_ = false;
   struct GraphEntry {
     int dir;  // 0 backward, 1 forward
     const void* in;

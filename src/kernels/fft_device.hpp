@@ -336,12 +336,14 @@ __device__ __forceinline__ void twiddle_powers(cx<T> w, cx<T> (&p)[R - 1]) {
 //  false: t fastest (a line's TP lanes adjacent; row-contiguous global access),
 //  true:  b fastest (B lines adjacent; column-contiguous global access, e.g. a
 //         stick's z-run or an intermediate column's y-run).
-template <typename T, int N, int S, bool LF = false, bool TwPre = true>
+// SS: the direction whose shape (CtShapeSel) the engine takes; the fused x
+// apply stage runs its forward engine on the backward engine's LDS geometry.
+template <typename T, int N, int S, bool LF = false, bool TwPre = true, int SS = S>
 struct FftCT {
   // line-fast engines (column access) take the precision-specific shape; the
   // row-mapped engine of the z stage keeps the default (fewer VGPRs per lane);
   // CtShapeSel overrides per stage kind where measured faster
-  using Sh = CtShapeSel<T, N, S, LF>;
+  using Sh = CtShapeSel<T, N, SS, LF>;
   static constexpr int E = Sh::E;
   static constexpr int TP = N / E;  // lanes per line
   static constexpr int PS = pad_shift<T>(E);
@@ -619,9 +621,9 @@ __host__ __device__ constexpr MrPlan mr_plan(int n, int emax, int minTp) {
 }
 
 // Same interface and lane mapping as FftCT (LF: lines fastest).
-template <typename T, int N, int S, bool LF = false>
+template <typename T, int N, int S, bool LF = false, int SS = S>
 struct FftMR {
-  static constexpr MrSel Sel = mr_sel<T, S, LF>();
+  static constexpr MrSel Sel = mr_sel<T, SS, LF>();  // (SS: as FftCT)
   static constexpr MrPlan P = mr_plan(N, Sel.emax, Sel.minTp);
   static_assert(P.np > 0, "length has no mixed-radix plan");
   static constexpr int NP = P.np;
@@ -764,10 +766,10 @@ struct FftMR {
 };
 
 // Compile-time engine core of a length: FftCT for powers of two, else FftMR.
-template <typename T, int N, int S, bool LF, bool TwPre = true>
+template <typename T, int N, int S, bool LF, bool TwPre = true, int SS = S>
 struct CtCore {
-  using type = typename std::conditional<(N & (N - 1)) == 0, FftCT<T, N, S, LF, TwPre>,
-                                         FftMR<T, N, S, LF>>::type;
+  using type = typename std::conditional<(N & (N - 1)) == 0, FftCT<T, N, S, LF, TwPre, SS>,
+                                         FftMR<T, N, S, LF, SS>>::type;
 };
 
 // ---------------------------------------------------------------- RT engine

@@ -138,6 +138,19 @@ void launch_x_backward(const XArgs& a, bool r2c, const cx<T>* inter, void* space
 template <typename T>
 void launch_x_forward(const XArgs& a, bool r2c, const void* space, cx<T>* inter, const cx<T>* tw,
                       const cx<T>* twHalf, hipStream_t stream);
+// Fused local-operator x stage of C2C transforms, in place on the intermediate:
+// inverse x FFT, multiply by the real potential [z][y][x] (rows as the space
+// domain's), forward x FFT. Batched launches take the potentials from
+// XArgs::batch.in and the intermediates from XArgs::batch.out. plainPotential:
+// default-policy loads of the potential (one potential shared by a batch)
+// instead of streaming ones.
+template <typename T>
+void launch_x_apply(const XArgs& a, const T* potential, cx<T>* inter, bool plainPotential,
+                    const cx<T>* tw, hipStream_t stream);
+// In-place multiply of a space domain by a real potential (unfused path).
+template <typename T>
+void launch_space_scale(void* space, const T* potential, long long count, bool realSpace,
+                        hipStream_t stream);
 
 // Largest run-time FFT length supported in one workgroup (LDS-resident).
 int max_device_fft_length(bool doublePrecision);

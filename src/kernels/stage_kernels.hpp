@@ -153,9 +153,11 @@ __device__ __forceinline__ void copy_out(const cx<T>* lds, int total, Src src, S
 // TwPre: the FftCT twiddle prefetch (off for the kernels where its registers
 // cost occupancy: the fp32 y forward kernels measured 61 -> 65 us at 256^3 and
 // 260 -> 384 us at 512^3 with it, 129+ VGPRs, one 512-thread workgroup per CU)
-template <typename T, int N, int S, bool LF = false, bool TwPre = true>
-struct CtEng {
-  using F = typename CtCore<T, N, S, LF, TwPre>::type;
+// SS: direction of the engine shape (FftCT); CtEng is the engine of a stage
+// with the shape of its own direction.
+template <typename T, int N, int S, bool LF, bool TwPre, int SS>
+struct CtEngS {
+  using F = typename CtCore<T, N, S, LF, TwPre, SS>::type;
   static constexpr int kN = N;
   static constexpr bool kBatchedCopy = false;
   static constexpr bool kLineFast = LF;
@@ -186,6 +188,8 @@ struct CtEng {
   static int h_threads() { return F::NT; }
   static std::size_t h_lds() { return F::lds_bytes(); }
 };
+template <typename T, int N, int S, bool LF = false, bool TwPre = true>
+struct CtEng : CtEngS<T, N, S, LF, TwPre, S> {};
 
 // Run-time length engine. LF (line-fast) engines walk the global side with the
 // line index fastest — consecutive lanes touch consecutive lines, i.e. the
@@ -1272,6 +1276,130 @@ __global__ void __launch_bounds__(Eng::kBlock)
   else
     stage_rows(eng, lds, yl, n, RowSrc<cx<T>>{static_cast<const cx<T>*>(space) + row0, n});
   eng.lds_to_global(lds, tw, store);
+}
+
+// Fused local-operator x stage (C2C): inverse x FFT of the tile's rows, multiply
+// by the real potential V[z][y][x], forward x FFT, all in LDS; the space domain
+// is neither written nor read. forward_twin(eng) is the forward engine that
+// runs on the LDS lines of the backward engine `eng`: same lines, line stride,
+// padding and threads. The host makes it and passes it as a kernel argument of
+// its own (a run-time plan copied inside the kernel would live in scratch: its
+// radix table is indexed).
+template <typename T, int N, bool LF, bool TwPre>
+__host__ __device__ inline CtEngS<T, N, -1, LF, TwPre, +1> forward_twin(const CtEng<T, N, +1, LF, TwPre>&) {
+  using FB = typename CtEng<T, N, +1, LF, TwPre>::F;
+  using FF = typename CtEngS<T, N, -1, LF, TwPre, +1>::F;
+  static_assert(FB::B == FF::B && FB::LS == FF::LS && FB::PS == FF::PS && FB::NT == FF::NT,
+                "x apply: the inverse and forward engines must share one LDS layout");
+  return {};
+}
+template <typename T, bool LF>
+__host__ __device__ inline RtEng<T, -1, LF> forward_twin(const RtEng<T, +1, LF>& e) {
+  return RtEng<T, -1, LF>{e.p};
+}
+template <typename T>
+__host__ __device__ inline BlueEng<T, -1> forward_twin(const BlueEng<T, +1>& e) {
+  return BlueEng<T, -1>{e.pm, e.nn, e.chirp, e.filt, e.twm};
+}
+
+// lds[dst(idx)] = lds[src(idx)] * v[idx] for idx in [0, total): lanes walk the
+// rows contiguously (the order of copy_out), so the loads of V coalesce and a
+// wave's LDS accesses are consecutive elements of one line. With the access
+// rules of tools/lds_bank_model.py the writes are conflict-free in both
+// precisions and the fp32 reads too; the fp64 reads of padded lines take 8
+// cycles per wave instead of 4 (a pad element falls inside every ds_read_b128
+// lane group), as in copy_out: 8 reads per lane, about 2 of the stage's 123 us
+// at 256^3 (profiles/r7/apply_local). kApplyUnroll loads of V are in flight per
+// lane. No LDS race: lane idx reads src(idx) and writes dst(idx), and the kernel
+// calls this with src = the inverse engine's out_at and dst = the forward
+// engine's in_at, which are either the same slot (compile-time engines: out_at
+// == in_at on one layout, which the static_assert of forward_twin guarantees;
+// in-place run-time plans; Bluestein) or slots of two disjoint LDS regions
+// (ping-pong run-time plans with an odd pass count). A shared shape whose out_at
+// and in_at differ inside one region would need a barrier-separated copy instead.
+// Stream: V is read once (non-temporal); plain loads for a potential shared by a
+// batch.
+constexpr int kApplyUnroll = 8;
+template <bool Stream, typename T, class Src, class Dst>
+__device__ __forceinline__ void scale_rows(cx<T>* lds, const T* __restrict__ v, int total, Src src, Dst dst) {
+  for (int base = threadIdx.x; base < total; base += blockDim.x * kApplyUnroll) {
+    T w[kApplyUnroll];
+#pragma unroll
+    for (int u = 0; u < kApplyUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        if constexpr (Stream) w[u] = ld_stream_real(v + idx);
+        else w[u] = v[idx];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kApplyUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) lds[dst(idx)] = scale(lds[src(idx)], w[u]);
+    }
+  }
+}
+
+// In place on the [z][column][y] intermediate: a workgroup owns the tile of
+// x_backward_kernel / x_forward_kernel (plane z, rows y0..y0+B, every column).
+// Invariant that makes the in-place update safe: the inverse FFT's first pass
+// reads every element of the tile before the forward FFT stores any, with the
+// multiply's barriers in between, and no other workgroup touches the tile.
+template <class Eng, class Fwd, typename T, bool StreamV>
+__global__ void __launch_bounds__(Eng::kBlock)
+    x_apply_kernel(Eng eng, Fwd fwd, XArgs a, const T* __restrict__ potential, cx<T>* inter,
+                   const cx<T>* __restrict__ tw) {
+  SPFFT_LDS_DECL(T);
+  SPFFT_BATCH_SELECT(a, potential, inter);
+  const int B = eng.lines();
+  const int n = eng.n();
+  int tx, ty;
+  block_tile(tx, ty);
+  const int zl = a.zBegin + ty;
+  const int y0 = tx * B;
+  int* xCol = reinterpret_cast<int*>(reinterpret_cast<char*>(lds) + eng.lds_bytes());
+  build_xcol(a, xCol, n);
+  cx<T>* tile = inter + static_cast<long long>(zl) * a.interZStride + y0;
+  const int yl = min(B, a.Y - y0);
+  // per-element arguments pinned in scalar registers (see x_backward_kernel)
+  const int rowStride = pin_uniform(static_cast<int>(a.interStride)), nFreq = pin_uniform(a.nFreq);
+  const int dense = pin_uniform(x_dense(a) ? 1 : 0);
+  auto col_of = [&](int x) { return dense ? (x < nFreq ? x : -1) : xCol[x]; };
+  auto load = [&](int b, int pos) -> cx<T> {
+    if (b >= yl) return czero<T>();
+    const int c = col_of(pos);
+    return c < 0 ? czero<T>() : ld_inter(&tile[c * rowStride + b]);
+  };
+  auto store = [&](int b, int pos, cx<T> v) {
+    const int c = col_of(pos);
+    if (c >= 0 && b < yl) st_inter(&tile[c * rowStride + b], v);
+  };
+  eng.global_to_lds(lds, tw, load);  // rows at out_at(b, x); ends with a barrier
+  const T* v = potential + (static_cast<long long>(zl) * a.Y + y0) * n;
+  scale_rows<StreamV>(lds, v, yl * n, [&](int idx) {
+    const int b = idx / n;
+    return eng.out_at(b, idx - b * n);
+  }, [&](int idx) {
+    const int b = idx / n;
+    return fwd.in_at(b, idx - b * n);
+  });
+  __syncthreads();
+  fwd.lds_to_global(lds, tw, store);
+}
+
+// In-place multiply of the space domain by a real potential (the unfused
+// local-operator path: R2C transforms and long x lines): E = cx<T> or T.
+template <typename E, typename T>
+__global__ void __launch_bounds__(256)
+    space_scale_kernel(E* __restrict__ space, const T* __restrict__ potential, long long count) {
+  const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
+  for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride) {
+    const T w = ld_stream_real(potential + i);
+    if constexpr (std::is_same<E, T>::value)
+      st_stream_real(space + i, ld_stream_real(space + i) * w);
+    else
+      st_stream(space + i, scale(ld_stream(space + i), w));
+  }
 }
 
 // Packed-real x stage (R2C transforms with even dimX): a real row of length n

@@ -129,5 +129,39 @@ void launch_x_forward(const XArgs& a, bool r2c, const void* space, cx<T>* inter,
   });
 }
 
+// Fused local-operator x stage (C2C, in place on the intermediate). The inverse
+// and the forward engine share the backward stage's shape (forward_twin).
+template <typename T>
+void launch_x_apply(const XArgs& a, const T* potential, cx<T>* inter, bool plainPotential,
+                    const cx<T>* tw, hipStream_t stream) {
+  if (a.L <= a.zBegin || a.Y <= 0) return;
+  with_engine<T, +1, true>(a.n, [&](auto eng, int threads, int lines, std::size_t lds) {
+    auto fwd = forward_twin(eng);
+    using E = decltype(eng);
+    using F = decltype(fwd);
+    auto k = plainPotential ? x_apply_kernel<E, F, T, false> : x_apply_kernel<E, F, T, true>;
+    const std::size_t ldsTotal = lds + std::size_t(a.n) * sizeof(int) + 16;
+    prepare_kernel(k, ldsTotal);
+    hipLaunchKernelGGL(k, dim3(ceil_div(a.Y, lines), a.L - a.zBegin, batch_dim(a.batch)), dim3(threads), ldsTotal, stream, eng, fwd, a,
+                       potential, inter, tw);
+    gpu_check_launch("x_apply", stream);
+  });
+}
+
+// space[i] *= potential[i] over `count` elements (complex or, realSpace, real)
+template <typename T>
+void launch_space_scale(void* space, const T* potential, long long count, bool realSpace,
+                        hipStream_t stream) {
+  if (count <= 0) return;
+  const unsigned blocks = static_cast<unsigned>(std::min<long long>((count + 255) / 256, 256 * 64));
+  if (realSpace)
+    hipLaunchKernelGGL((space_scale_kernel<T, T>), dim3(blocks), dim3(256), 0, stream,
+                       static_cast<T*>(space), potential, count);
+  else
+    hipLaunchKernelGGL((space_scale_kernel<cx<T>, T>), dim3(blocks), dim3(256), 0, stream,
+                       static_cast<cx<T>*>(space), potential, count);
+  gpu_check_launch("space_scale", stream);
+}
+
 }  // namespace dev
 }  // namespace spfft
