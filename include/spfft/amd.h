@@ -167,6 +167,38 @@ SPFFT_EXPORT SpfftError spfft_amd_float_multi_transform_apply_local(
     int n, SpfftFloatTransform* transforms, const float* const* inputs,
     const float* const* potentials, float* const* outputs, const SpfftScalingType* scalings);
 
+/* Density accumulation: density[z][y][x] += weight * |backward(input)[z][y][x]|^2
+ * in one call, with the real array density over the local space domain
+ * [localZ][dimY][dimX] (double or float as the transform; for R2C the space
+ * value is real and the contribution weight * s^2). density is a host or device
+ * pointer, is updated in place and is never zeroed by the library; input is not
+ * modified. After the call the contents of the space domain are unspecified:
+ * fused plans (C2C transforms whose x lines fit one workgroup) never form it
+ * and leave it untouched, other plans (R2C, long x lines) pass through it. A
+ * null density with local planes is SPFFT_INVALID_PARAMETER_ERROR. */
+SPFFT_EXPORT SpfftError spfft_amd_transform_accumulate_density(SpfftTransform t,
+                                                               const double* input, double weight,
+                                                               double* density);
+SPFFT_EXPORT SpfftError spfft_amd_float_transform_accumulate_density(SpfftFloatTransform t,
+                                                                     const float* input,
+                                                                     float weight, float* density);
+/* *fused = 1 if the plan runs the fused x density stage on the GPU, else 0. */
+SPFFT_EXPORT SpfftError spfft_amd_transform_density_fused(SpfftTransform t, int* fused);
+SPFFT_EXPORT SpfftError spfft_amd_float_transform_density_fused(SpfftFloatTransform t, int* fused);
+/* density += sum_i weights[i] * |backward_i(inputs[i])|^2 of n transforms
+ * (distinct grids, equal space domains) into one shared density, with their
+ * phases interleaved; identical fused plans on one GPU share one launch per
+ * stage (SPFFT_BATCH). The sum runs in list order: the same call on the same
+ * data gives the same bits. */
+SPFFT_EXPORT SpfftError spfft_amd_multi_transform_accumulate_density(int n,
+                                                                     SpfftTransform* transforms,
+                                                                     const double* const* inputs,
+                                                                     const double* weights,
+                                                                     double* density);
+SPFFT_EXPORT SpfftError spfft_amd_float_multi_transform_accumulate_density(
+    int n, SpfftFloatTransform* transforms, const float* const* inputs, const float* weights,
+    float* density);
+
 /* Timer tree (SPFFT_TIMING=1 or spfft_amd_timing_enable). enable: 0 off, 1 host
  * scopes only (like the reference's timer), 2 host scopes and GPU stage times
  * (a hipEvent per stage boundary, nodes gpu/<direction>/<stage>). */

@@ -111,6 +111,30 @@ def _potential_ptr(v, prec: _Precision, shape):
     return arr.ctypes.data, arr
 
 
+def _density_ptr(rho, prec: _Precision, shape):
+    """Returns (address, keepalive) of a real density of the space domain's shape. The
+    array is written, so it is never copied: a wrong dtype is a TypeError, a wrong shape
+    or a non-contiguous array a ValueError."""
+    if rho is None:
+        return None, None
+    if _is_torch(rho):
+        if rho.dtype != prec.torch_real:
+            raise TypeError(f"density: expected {prec.torch_real}, got {rho.dtype}")
+        if tuple(rho.shape) != tuple(shape):
+            raise ValueError(f"density: expected shape {tuple(shape)}, got {tuple(rho.shape)}")
+        if not rho.is_contiguous():
+            raise ValueError("density must be contiguous")
+        return rho.data_ptr(), rho
+    if not isinstance(rho, np.ndarray) or rho.dtype != prec.real:
+        raise TypeError(f"density: expected a {np.dtype(prec.real)} array, got "
+                        f"{getattr(rho, 'dtype', type(rho).__name__)}")
+    if tuple(rho.shape) != tuple(shape):
+        raise ValueError(f"density: expected shape {tuple(shape)}, got {tuple(rho.shape)}")
+    if not rho.flags.c_contiguous or not rho.flags.writeable:
+        raise ValueError("density must be a writable C-contiguous array")
+    return rho.ctypes.data, rho
+
+
 class _GridBase:
     _single = False
 
@@ -398,6 +422,32 @@ class _TransformBase:
             c = self._cache["apply_local_fused"] = bool(v.value)
         return c
 
+    def accumulate_density(self, values, weight, density):
+        """density += weight * |backward(values)|**2 in one call (R2C: weight * s**2).
+
+        `density` is a real array (numpy or torch, host or device memory) of shape
+        space_domain_shape() and the transform's precision; it is updated in place,
+        never zeroed and never copied. `values` is not modified. The contents of the
+        space domain are unspecified afterwards; fused plans (see density_fused) never
+        form it and leave it untouched. Returns `density`."""
+        rptr, rkeep = _density_ptr(density, self._prec, self.space_domain_shape())
+        iptr, ikeep = _data_ptr(values, self._prec, False, "values")
+        _check(self._prec.amd_fn("transform_accumulate_density")(self._h, iptr, float(weight), rptr))
+        # asynchronous execution (set_stream(..., synchronous=False)) may still use them
+        self._step_keep = (ikeep, rkeep)
+        return density
+
+    @property
+    def density_fused(self) -> bool:
+        """True if accumulate_density runs the fused x stage (GPU, C2C, x lines of one
+        workgroup)."""
+        c = self._cache.get("density_fused")
+        if c is None:
+            v = ctypes.c_int()
+            _check(self._prec.amd_fn("transform_density_fused")(self._h, ctypes.byref(v)))
+            c = self._cache["density_fused"] = bool(v.value)
+        return c
+
     # --------------------------------------------------- streams / step API
     def set_stream(self, stream=None, synchronous: bool = True):
         """Execute on a HIP stream (int handle or torch.cuda.Stream; 0 = legacy default
@@ -538,3 +588,31 @@ def multi_transform_apply_local(transforms, inputs, potentials, outputs=None, sc
     for t in transforms:
         t._step_keep = keeps
     return outputs
+
+
+def multi_transform_accumulate_density(transforms, inputs, weights, density):
+    """density += sum_i weights[i] * |backward_i(inputs[i])|**2 of several independent
+    transforms (distinct grids, one space domain shape) into one shared `density`,
+    overlapped; identical fused plans on one GPU share one launch per stage. The sum
+    order is fixed by the call. Returns `density`."""
+    n, prec, arr = _multi(transforms)
+    if len(inputs) != n or len(weights) != n:
+        raise ValueError("one input and one weight per transform")
+    if any(t._single != prec.single for t in transforms):
+        raise TypeError("transforms of one call share one precision")
+    shape = transforms[0].space_domain_shape() if n else None
+    if any(tuple(t.space_domain_shape()) != tuple(shape) for t in transforms):
+        raise ValueError("transforms of one call share one space domain shape")
+    rptr, rkeep = _density_ptr(density, prec, shape) if n else (None, None)
+    keeps = [rkeep]
+    iptrs = (ctypes.c_void_p * max(1, n))()
+    for i in range(n):
+        iptrs[i], k = _data_ptr(inputs[i], prec, False, "values")
+        keeps.append(k)
+    ws = ((ctypes.c_float if prec.single else ctypes.c_double) * max(1, n))(
+        *[float(w) for w in weights])
+    _check(prec.amd_fn("multi_transform_accumulate_density")(
+        n, arr, iptrs, ctypes.cast(ws, ctypes.c_void_p), rptr))
+    for t in transforms:
+        t._step_keep = keeps
+    return density

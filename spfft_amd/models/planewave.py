@@ -126,12 +126,31 @@ class PlaneWaveModel:
             out.extend(r.clone() if hasattr(r, "clone") else np.array(r) for r in res)
         return out
 
-    def density(self, psi: Sequence, weights: Sequence[float]):
-        """rho(r) = sum_b w_b |psi_b(r)|^2 on the real-space grid [z][y][x]."""
-        from ..grid import multi_transform_backward
+    def density(self, psi: Sequence, weights: Sequence[float], unfused: bool = False):
+        """rho(r) = sum_b w_b |psi_b(r)|^2 on the real-space grid [z][y][x].
+
+        One multi_transform_accumulate_density call per group of bands into a
+        zeroed rho of the transforms' precision, allocated where the transforms
+        run (on the GPU the x stage adds w |psi|^2 to its rows of rho from LDS and
+        the space domain is never formed); `unfused` runs the composition
+        backward, |psi|^2, sum instead."""
+        from ..grid import multi_transform_accumulate_density, multi_transform_backward
         rho = None
         T = len(self.transforms)
         psi, weights = list(psi), list(weights)
+        if not unfused:
+            t0 = self.transforms[0]
+            if self.pu == ProcessingUnit.GPU:
+                import torch
+                dev = psi[0].device if psi and getattr(psi[0], "is_cuda", False) else "cuda"
+                rho = torch.zeros(t0.space_domain_shape(), dtype=t0._prec.torch_real, device=dev)
+            else:
+                rho = np.zeros(t0.space_domain_shape(), dtype=t0._prec.real)
+            for start in range(0, len(psi), T):
+                group = psi[start:start + T]
+                multi_transform_accumulate_density(self.transforms[:len(group)], group,
+                                                   weights[start:start + T], rho)
+            return rho
         for start in range(0, len(psi), T):
             group = psi[start:start + T]
             spaces = multi_transform_backward(self.transforms[:len(group)], group)

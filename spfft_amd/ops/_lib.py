@@ -123,6 +123,10 @@ def _prototypes(lib):
         sig[pre + "transform_apply_local_fused"] = [V, c_int_p]
         sig[pre + "multi_transform_apply_local"] = [I, c_void_pp, c_void_pp, c_void_pp, c_void_pp,
                                                     c_int_p]
+    for pre, real in (("spfft_amd_", ctypes.c_double), ("spfft_amd_float_", ctypes.c_float)):
+        sig[pre + "transform_accumulate_density"] = [V, D, real, D]
+        sig[pre + "transform_density_fused"] = [V, c_int_p]
+        sig[pre + "multi_transform_accumulate_density"] = [I, c_void_pp, c_void_pp, D, D]
     sig["spfft_amd_timing_enable"] = [I]
     sig["spfft_amd_timing_reset"] = []
     sig["spfft_amd_timing_json"] = [ctypes.c_char_p, ctypes.c_size_t, c_size_t_p]

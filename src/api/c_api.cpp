@@ -39,6 +39,10 @@ void multi_apply_local_handles(int n, Transform** ts, const double* const* in,
 void multi_apply_local_handles(int n, TransformFloat** ts, const float* const* in,
                                const float* const* pot, float* const* out,
                                const SpfftScalingType* sc);
+void multi_accumulate_density_handles(int n, Transform** ts, const double* const* in,
+                                      const double* weights, double* density);
+void multi_accumulate_density_handles(int n, TransformFloat** ts, const float* const* in,
+                                      const float* weights, float* density);
 }  // namespace spfft
 
 using namespace spfft;
@@ -553,6 +557,51 @@ SpfftError spfft_amd_float_multi_transform_apply_local(int n, SpfftFloatTransfor
   return guarded([&] {
     multi_apply_local_handles(n, reinterpret_cast<TransformFloat**>(transforms), inputs, potentials,
                               outputs, scalings);
+  });
+}
+
+SpfftError spfft_amd_transform_accumulate_density(SpfftTransform t, const double* input,
+                                                  double weight, double* density) {
+  return with_handle<Transform>(
+      t, [&](Transform& x) { x.impl()->accumulate_density(input, weight, density); });
+}
+SpfftError spfft_amd_float_transform_accumulate_density(SpfftFloatTransform t, const float* input,
+                                                        float weight, float* density) {
+  return with_handle<TransformFloat>(
+      t, [&](TransformFloat& x) { x.impl()->accumulate_density(input, weight, density); });
+}
+SpfftError spfft_amd_transform_density_fused(SpfftTransform t, int* fused) {
+  if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
+  return with_handle<Transform>(t,
+                                [&](Transform& x) { *fused = x.impl()->density_fused() ? 1 : 0; });
+}
+SpfftError spfft_amd_float_transform_density_fused(SpfftFloatTransform t, int* fused) {
+  if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
+  return with_handle<TransformFloat>(
+      t, [&](TransformFloat& x) { *fused = x.impl()->density_fused() ? 1 : 0; });
+}
+SpfftError spfft_amd_multi_transform_accumulate_density(int n, SpfftTransform* transforms,
+                                                        const double* const* inputs,
+                                                        const double* weights, double* density) {
+  if (n > 0 && !transforms) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < n; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_accumulate_density_handles(n, reinterpret_cast<Transform**>(transforms), inputs, weights,
+                                     density);
+  });
+}
+SpfftError spfft_amd_float_multi_transform_accumulate_density(int n,
+                                                              SpfftFloatTransform* transforms,
+                                                              const float* const* inputs,
+                                                              const float* weights,
+                                                              float* density) {
+  if (n > 0 && !transforms) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < n; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_accumulate_density_handles(n, reinterpret_cast<TransformFloat**>(transforms), inputs,
+                                     weights, density);
   });
 }
 

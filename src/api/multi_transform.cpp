@@ -210,6 +210,67 @@ void multi_apply_local(const std::vector<TransformImpl<T>*>& ts, const T* const*
     if (ts[i]->is_gpu() && ts[i]->gpu()->synchronous()) ts[i]->synchronize();
 }
 
+// density += sum_i weights[i] |backward_i(inputs[i])|^2 into one shared rho, phases
+// interleaved like multi_apply_local. The transforms update the same array, so
+// their density stages run one after another: batches first (in group order),
+// then the other GPU transforms and the host transforms in list order; `last`
+// is the GPU executor whose stream holds the latest update, and the next stage
+// on another stream waits for it by an event. The order depends on the call
+// alone, so the same call on the same data gives the same bits.
+template <typename T>
+void multi_accumulate_density(const std::vector<TransformImpl<T>*>& ts, const T* const* inputs,
+                              const T* weights, T* density) {
+  SPFFT_TIMED_SCOPE("multi_accumulate_density");
+  check_distinct_grids(ts);
+  const int n = static_cast<int>(ts.size());
+  if (n > 0 && (!inputs || !weights)) throw InvalidParameterError();
+  for (int i = 0; i < n; ++i)
+    if (!density && ts[i]->plan().local_planes() > 0) throw InvalidParameterError();
+  GpuExecutor<T>* last = nullptr;
+  const bool deviceRho = density && is_device_pointer(density);
+  const std::vector<bool> batched = run_batches<T>(
+      ts,
+      [&](int i) {
+        return ts[i]->density_fused() && deviceRho &&
+               (ts[i]->plan().numLocalElements == 0 || is_device_pointer(inputs[i]));
+      },
+      [](int) { return 0; },
+      [&](const std::vector<int>& g) {
+        std::vector<GpuExecutor<T>*> ex;
+        std::vector<const T*> ins;
+        std::vector<T> ws;
+        for (int j : g) {
+          ex.push_back(ts[j]->gpu());
+          ins.push_back(inputs[j]);
+          ws.push_back(weights[j]);
+        }
+        GpuExecutor<T>::accumulate_density_batch(ex, ins, ws, density, last);
+        last = ex[0];
+      });
+  for (int i = 0; i < n; ++i)
+    if (ts[i]->is_gpu() && !batched[i]) ts[i]->backward_z(inputs[i]);
+  for (int i = 0; i < n; ++i)
+    if (!ts[i]->is_gpu()) {
+      ts[i]->backward_z(inputs[i]);
+      ts[i]->backward_exchange(true);
+    }
+  for (int i = 0; i < n; ++i)
+    if (ts[i]->is_gpu() && !batched[i]) {
+      ts[i]->backward_exchange(true);
+      ts[i]->gpu()->accumulate_density_xy(density, weights[i], last);
+      last = ts[i]->gpu();
+    }
+  for (int i = 0; i < n; ++i)
+    if (!ts[i]->is_gpu()) {
+      // a host transform updates rho on the calling thread: behind the GPU transforms' updates
+      if (last) last->synchronize();
+      last = nullptr;
+      ts[i]->accumulate_density_xy(density, weights[i]);
+    }
+  for (int i = 0; i < n; ++i)
+    if (ts[i]->is_gpu() && ts[i]->gpu()->synchronous()) ts[i]->synchronize();
+}
+
 template <typename TR, typename T>
 std::vector<TransformImpl<T>*> impls(int n, TR* transforms) {
   if (n < 0 || (n > 0 && !transforms)) throw InvalidParameterError();
@@ -273,6 +334,20 @@ void multi_apply_local_handles(int n, TransformFloat** ts, const float* const* i
   std::vector<TransformImpl<float>*> v;
   for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
   multi_apply_local<float>(v, in, pot, out, sc);
+}
+void multi_accumulate_density_handles(int n, Transform** ts, const double* const* in,
+                                      const double* weights, double* density) {
+  if (n < 0 || (n > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<double>*> v;
+  for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_accumulate_density<double>(v, in, weights, density);
+}
+void multi_accumulate_density_handles(int n, TransformFloat** ts, const float* const* in,
+                                      const float* weights, float* density) {
+  if (n < 0 || (n > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<float>*> v;
+  for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_accumulate_density<float>(v, in, weights, density);
 }
 void multi_forward_handles(int n, TransformFloat** ts, SpfftProcessingUnitType* in, float** out,
                            SpfftScalingType* sc) {

@@ -137,6 +137,36 @@ void TransformImpl<T>::apply_local_xy(const T* potential) {
 }
 
 template <typename T>
+void TransformImpl<T>::accumulate_density(const T* input, T weight, T* density) {
+  SPFFT_TIMED_SCOPE("accumulate_density");
+  if (!density && plan_->local_planes() > 0) throw InvalidParameterError();
+  backward_z(input);
+  backward_exchange(false);
+  accumulate_density_xy(density, weight);
+  if (gpu_ && gpu_->synchronous()) gpu_->synchronize();
+}
+
+template <typename T>
+void TransformImpl<T>::accumulate_density_xy(T* density, T weight) {
+  const IndexPlan& p = *plan_;
+  if (!density && p.local_planes() > 0) throw InvalidParameterError();
+  if (gpu_) {
+    gpu_->accumulate_density_xy(density, weight);
+    return;
+  }
+  // host: the plain composition through the space domain
+  host_->backward_xy();
+  const std::size_t count = static_cast<std::size_t>(p.local_planes()) * p.dimY * p.dimX;
+  const T* space = host_->space_domain();
+  if (p.type == SPFFT_TRANS_R2C) {
+    for (std::size_t i = 0; i < count; ++i) density[i] += weight * (space[i] * space[i]);
+  } else {
+    for (std::size_t i = 0; i < count; ++i)
+      density[i] += weight * (space[2 * i] * space[2 * i] + space[2 * i + 1] * space[2 * i + 1]);
+  }
+}
+
+template <typename T>
 void TransformImpl<T>::forward_xy(SpfftProcessingUnitType inputLocation) {
   if (host_) {
     if (inputLocation != SPFFT_PU_HOST) throw InvalidParameterError();

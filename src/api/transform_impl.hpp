@@ -32,6 +32,15 @@ public:
   // the stage between the two exchanges of apply_local (multi-transform interleaving)
   void apply_local_xy(const T* potential);
 
+  // density[z][y][x] += weight * |backward(input)[z][y][x]|^2 over the local
+  // space domain (R2C: weight * s^2); density is updated in place, input is not
+  // modified, the space domain's contents are unspecified afterwards (untouched
+  // on the fused GPU path)
+  void accumulate_density(const T* input, T weight, T* density);
+  bool density_fused() const { return gpu_ && gpu_->density_fused(); }
+  // the stage behind backward_exchange (multi-transform interleaving)
+  void accumulate_density_xy(T* density, T weight);
+
   void forward_xy(SpfftProcessingUnitType inputLocation);
   void forward_exchange(bool nonBlocking);
   void forward_z(T* output, SpfftScalingType scaling);

@@ -68,6 +68,8 @@ GpuExecutor<T>::GpuExecutor(std::shared_ptr<GridImpl<T>> grid,
   // apply_local runs the fused x apply stage for C2C transforms whose x lines
   // fit one workgroup; R2C (packed-real pair) and long x lines run unfused
   applyFused_ = p.type == SPFFT_TRANS_C2C && !longX_;
+  // accumulate_density runs the fused x density stage under the same conditions
+  densityFused_ = applyFused_;
   // Backward z -> y hand-off through the Infinity Cache: a single rank's z
   // stage writes the stick array that its y stage reads next. With the default
   // cache policy on both sides (instead of streaming) and a stick array that
@@ -222,7 +224,7 @@ void GpuExecutor<T>::log_plan() const {
   if (p.size > 1) plane = const_cast<GridImpl<T>&>(*grid_).device_comm().describe();
   std::fprintf(stderr,
                "spfft[gpu rank %d/%d] %dx%dx%d %s %s: sticks=%d planes=%d columns=%d | z{%s} "
-               "y{%s} x{%s}%s inter_planes=%d apply_local=%s | exchange=%s%s plane=%s chunks=%d stick_blocks=%d "
+               "y{%s} x{%s}%s inter_planes=%d apply_local=%s density=%s | exchange=%s%s plane=%s chunks=%d stick_blocks=%d "
                "steps=%zu+%zu (%.2f MB per peer) peer_writes=%d peer_offsets=[%lld, %lld] "
                "library_streams=%d\n",
                p.rank, p.size, p.dimX, p.dimY, p.dimZ,
@@ -231,6 +233,7 @@ void GpuExecutor<T>::log_plan() const {
                describe(longZ_, lpZ_, p.dimZ, false).c_str(), describe(longY_, lpY_, p.dimY, true).c_str(),
                describe(longX_, lpX_, twXh_ ? p.dimX / 2 : p.dimX, true).c_str(),
                twXh_ ? " packed-real" : "", interPlanes_, applyFused_ ? "fused" : "unfused",
+               densityFused_ ? "fused" : "composed",
                layout_.buffered ? "buffered" : "compact",
                floatExchange_ ? "-float" : "", plane.c_str(), exchChunks_, stickBlocks_, bwdSteps_.size(),
                fwdSteps_.size(), chunkModel_ / 1e6, peerWrites_ ? 1 : 0, peerOffsetRange_[0],
@@ -1368,6 +1371,79 @@ void GpuExecutor<T>::apply_local_xy(const T* potential) {
   stage_mark("forward", nullptr);
 }
 
+// --------------------------------------------------------------------- density
+// accumulate_density = backward_z, backward_exchange, accumulate_density_xy
+// (TransformImpl::accumulate_density). Fused plans (C2C, x lines of one
+// workgroup) never form the space domain: per plane range of the intermediate
+// y backward and x density (inverse x FFT in LDS, rho += w |psi|^2 on the
+// workgroup's rows of rho). Other plans run backward_xy and one pass over the
+// space domain. A host rho is staged through a device buffer on the stream.
+template <typename T>
+void GpuExecutor<T>::order_after_density(GpuExecutor* prev) {
+  if (!prev || prev == this || prev->stream_ == stream_) return;
+  if (!prev->densityEvent_) prev->densityEvent_.reset(new GpuEvent());
+  prev->densityEvent_->record(prev->stream_);
+  prev->densityEvent_->wait_on(stream_);
+}
+
+template <typename T>
+void GpuExecutor<T>::accumulate_density_xy(T* density, T weight, GpuExecutor* after) {
+  SPFFT_TIMED_SCOPE("gpu_accumulate_density_xy");
+  DeviceGuard guard(deviceId_);
+  const IndexPlan& p = *plan_;
+  const std::size_t count = static_cast<std::size_t>(p.local_planes()) * p.dimY * p.dimX;
+  if (count > 0 && !density) throw InvalidParameterError();
+  T* rho = density;
+  const bool staged = count > 0 && !is_device_pointer(density);
+  if (staged) {
+    if (!density_ || density_->bytes() < count * sizeof(T))
+      density_.reset(new DeviceBuffer(count * sizeof(T)));
+    rho = density_->data<T>();
+    order_after_density(after);  // its download of this rho
+    after = nullptr;
+    gpu_check(hipMemcpyAsync(rho, density, count * sizeof(T), hipMemcpyHostToDevice, stream_),
+              "hipMemcpyAsync");
+  }
+  if (!densityFused_) {
+    backward_xy(SPFFT_PU_GPU);
+    order_after_density(after);
+    dev::launch_space_density<T>(grid_->device_slot(GridImpl<T>::kSpace), rho, weight,
+                                 static_cast<long long>(count), p.type == SPFFT_TRANS_R2C, stream_);
+    stage_mark("backward", "density");
+  } else {
+    const bool pipe = pipelined();
+    StageEnd stageEnd{this, "backward", pipe ? "exchange+y+x_density" : "y+x_density"};
+    void* slab = grid_->device_slot(GridImpl<T>::kSlabSide);
+    auto* inter = static_cast<cx<T>*>(grid_->device_slot(GridImpl<T>::kInter));
+    if (peerWrites_) grid_->device_comm().note_read(GridImpl<T>::kSlabSide);
+    const int K = pipe ? exchChunks_ : 1;
+    for (int k = 0; k < K; ++k) {
+      if (pipe) chunkEv_[k]->wait_on(stream_);  // chunk k has arrived
+      const int zb = pipe ? planeBounds_[k] : 0;
+      const int ze = pipe ? planeBounds_[k + 1] : p.local_planes();
+      for (int z0 = zb; z0 < ze; z0 += interPlanes_) {
+        auto ya = yargs();
+        auto xa = xargs();
+        ya.zBegin = xa.zBegin = z0;
+        ya.L = xa.L = std::min(ze, z0 + interPlanes_);
+        if (pipe) {
+          ya.colBase = colBaseChunk_[k] ? colBaseChunk_[k]->data<long long>() : nullptr;
+          set_col_desc(ya, colDescChunk_[k]);
+        }
+        ya.plainSticks = plainHandoff_;
+        cx<T>* tile = inter_for(inter, z0);
+        y_backward_launch(ya, slab, tile);
+        order_after_density(after);  // (once: the stream stays behind it)
+        after = nullptr;
+        dev::launch_x_density<T>(xa, tile, rho, &weight, twX_->data<cx<T>>(), stream_);
+      }
+    }
+  }
+  if (staged)
+    gpu_check(hipMemcpyAsync(density, rho, count * sizeof(T), hipMemcpyDeviceToHost, stream_),
+              "hipMemcpyAsync");
+}
+
 // ------------------------------------------------------- batched multi-transform
 namespace {
 struct Fnv {
@@ -1623,6 +1699,56 @@ void GpuExecutor<T>::apply_local_batch(const std::vector<GpuExecutor*>& ex,
   za.batch = zf;
   dev::launch_z_forward<T, cx<T>>(za, static_cast<const cx<T>*>(zf.in[0]),
                                   static_cast<cx<T>*>(zf.out[0]), factor, l->twZ_->data<cx<T>>(), s);
+  batch_release(ex);
+}
+
+// One launch per stage for a batch of fused plans that accumulate into one
+// rho: z backward, y backward, then one x density launch whose workgroups loop
+// over the bands for their tile of rho (the bands share rho, so they are not
+// spread over the grid).
+template <typename T>
+void GpuExecutor<T>::accumulate_density_batch(const std::vector<GpuExecutor*>& ex,
+                                              const std::vector<const T*>& inputs,
+                                              const std::vector<T>& weights, T* density,
+                                              GpuExecutor* after) {
+  SPFFT_TIMED_SCOPE("gpu_accumulate_density_batch");
+  const int n = static_cast<int>(ex.size());
+  if (n < 1 || n > dev::kMaxBatch || inputs.size() != ex.size() || weights.size() != ex.size())
+    throw InternalError();
+  GpuExecutor* l = ex[0];
+  DeviceGuard guard(l->deviceId_);
+  for (GpuExecutor* e : ex)
+    if (!e->batchable() || !e->densityFused_ || e->batchKey_ != l->batchKey_) throw InternalError();
+  const IndexPlan& p = *l->plan_;
+  if (p.local_planes() > 0 && (!density || !is_device_pointer(density))) throw InvalidParameterError();
+  batch_join(ex);
+  dev::BatchPtrs zb{}, yb{}, xb{};
+  zb.count = yb.count = xb.count = n;
+  for (int i = 0; i < n; ++i) {
+    GpuExecutor* e = ex[i];
+    if (p.numLocalElements > 0 && (!inputs[i] || !is_device_pointer(inputs[i])))
+      throw InvalidParameterError();
+    zb.in[i] = inputs[i];
+    zb.out[i] = e->grid_->device_slot(GridImpl<T>::kStickSide);
+    yb.in[i] = e->grid_->device_slot(GridImpl<T>::kSlabSide);
+    yb.out[i] = e->grid_->device_slot(GridImpl<T>::kInter);
+    xb.in[i] = yb.out[i];
+    xb.out[i] = nullptr;  // the bands share `density`
+  }
+  auto za = l->zargs();
+  auto ya = l->yargs();
+  auto xa = l->xargs();
+  za.batch = zb;
+  ya.batch = yb;
+  xa.batch = xb;
+  hipStream_t s = l->stream_;
+  dev::launch_z_backward<T, cx<T>>(za, static_cast<const cx<T>*>(zb.in[0]),
+                                   static_cast<cx<T>*>(zb.out[0]), l->twZ_->data<cx<T>>(), s);
+  dev::launch_y_backward<T, cx<T>>(ya, static_cast<const cx<T>*>(yb.in[0]),
+                                   static_cast<cx<T>*>(yb.out[0]), l->twY_->data<cx<T>>(), s);
+  l->order_after_density(after);
+  dev::launch_x_density<T>(xa, static_cast<const cx<T>*>(xb.in[0]), density, weights.data(),
+                           l->twX_->data<cx<T>>(), s);
   batch_release(ex);
 }
 

@@ -74,6 +74,24 @@ public:
                                 const std::vector<const T*>& potentials, const std::vector<T*>& outputs,
                                 SpfftScalingType scaling);
 
+  // Density accumulation (TransformImpl::accumulate_density): the stage behind
+  // backward_exchange, density[z][y][x] += weight |space value|^2 over the local
+  // slab. Fused plans run y backward and the x density stage (inverse x FFT in
+  // LDS, read-modify-write of the workgroup's rows of rho) per plane range and
+  // leave the space domain untouched; other plans (R2C, long x lines) run
+  // backward_xy and one pass over the space domain. `density` is a host or
+  // device pointer (a host array is staged on the stream).
+  // `after`: the executor whose stream holds the latest update of this rho
+  // (multi-transform calls); the update is ordered behind it.
+  void accumulate_density_xy(T* density, T weight, GpuExecutor* after = nullptr);
+  bool density_fused() const { return densityFused_; }
+  // batchable() fused plans with equal keys into one rho: one launch per stage,
+  // the x density workgroups loop over the members in order (device pointers)
+  static void accumulate_density_batch(const std::vector<GpuExecutor*>& ex,
+                                       const std::vector<const T*>& inputs,
+                                       const std::vector<T>& weights, T* density,
+                                       GpuExecutor* after = nullptr);
+
   void synchronize();
   bool synchronous() const { return synchronous_; }
   // Execute on `stream` (nullptr = the legacy default stream); work is then
@@ -109,6 +127,10 @@ private:
   const T* device_potential(const T* potential);  // stages a host potential
   std::unique_ptr<DeviceBuffer> potential_;
   bool applyFused_ = false;
+  std::unique_ptr<DeviceBuffer> density_;  // stages a host rho
+  bool densityFused_ = false;
+  void order_after_density(GpuExecutor* prev);  // this stream waits for prev's work so far
+  std::unique_ptr<GpuEvent> densityEvent_;
   struct GraphEntry {
     int dir;  // 0 backward, 1 forward
     const void* in;

@@ -152,6 +152,19 @@ template <typename T>
 void launch_space_scale(void* space, const T* potential, long long count, bool realSpace,
                         hipStream_t stream);
 
+// Fused density x stage of C2C transforms: density[z][y][x] += weights[m] *
+// |inverse x FFT of band m's intermediate|^2. Unbatched: one band (`inter`,
+// weights[0]). Batched launches take the bands' intermediates from
+// XArgs::batch.in and batch.count weights; the bands share `density`, so every
+// workgroup loops over them for its tile (the grid is the unbatched grid).
+template <typename T>
+void launch_x_density(const XArgs& a, const cx<T>* inter, T* density, const T* weights,
+                      const cx<T>* tw, hipStream_t stream);
+// density[i] += weight * |space[i]|^2 in one pass (composed path).
+template <typename T>
+void launch_space_density(const void* space, T* density, T weight, long long count, bool realSpace,
+                          hipStream_t stream);
+
 // Largest run-time FFT length supported in one workgroup (LDS-resident).
 int max_device_fft_length(bool doublePrecision);
 // true if n has a compile-time (register-resident) kernel: the powers of two

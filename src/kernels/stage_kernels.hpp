@@ -1402,6 +1402,175 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// Fused density x stage (C2C): rho[z][y][x] += w |backward(values)[z][y][x]|^2
+// with the inverse x FFT of the tile's rows in LDS; the space domain is neither
+// written nor read. Weights of a batched launch, by value.
+template <typename T>
+struct DensityWeights {
+  T w[kMaxBatch];
+};
+template <typename T>
+__device__ __forceinline__ T norm2(cx<T> v) {
+  return fma(v.x, v.x, v.y * v.y);
+}
+
+// rho[idx] = fma(w, |lds[src(idx)]|^2, rho[idx]) for idx in [0, total): lanes
+// walk the rows contiguously (the order of copy_out), so the accesses of rho
+// coalesce; kDensityUnroll loads of rho are in flight per lane before the first
+// dependent store (the compiler may not move a load of rho over a store to it).
+// The unroll is kept small: copy_out's fully unrolled tile on top of the rho
+// values doubled the kernel's VGPRs against x_backward_kernel (N = 128 fp64:
+// 140 against 69) and spilled at N = 1024. Stream: rho is read and written once
+// per launch (non-temporal); plain accesses when the bands of a batch revisit
+// the tile.
+constexpr int kDensityUnroll = 4;
+template <bool Stream, typename T, class Src>
+__device__ __forceinline__ void density_rows(const cx<T>* lds, T* __restrict__ rho, T w, int total, Src src) {
+  for (int base = threadIdx.x; base < total; base += blockDim.x * kDensityUnroll) {
+    T r[kDensityUnroll];
+#pragma unroll
+    for (int u = 0; u < kDensityUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        if constexpr (Stream) r[u] = ld_stream_real(rho + idx);
+        else r[u] = rho[idx];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kDensityUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        const T v = fma(w, norm2(lds[src(idx)]), r[u]);
+        if constexpr (Stream) st_stream_real(rho + idx, v);
+        else rho[idx] = v;
+      }
+    }
+  }
+}
+
+// A workgroup owns the tile of x_backward_kernel (plane z, rows y0..y0+B, every
+// column) and with it the rows of rho: no other workgroup of the launch touches
+// them, so the update needs no atomics. The bands of a batched launch share
+// rho, so they are not spread over blockIdx.z: the workgroup loops over them
+// for its tile (intermediates from XArgs::batch.in), and lane idx updates the
+// same elements of rho for every band, in band order (in registers for full
+// tiles of compile-time engines, else in rho itself, where a band's update is
+// ordered behind the previous one's by the lane's own program order): the
+// sum order is fixed. StreamRho: the cache policy of the rho accesses (a template
+// parameter: a run-time flag costs registers, profiles/r6/ntmerge). Batched:
+// the band loop; a single-band launch runs the body once without it, with the
+// register budget of x_backward_kernel.
+template <class Eng, typename T, bool StreamRho, bool Batched>
+__global__ void __launch_bounds__(Eng::kBlock)
+    x_density_kernel(Eng eng, XArgs a, const cx<T>* __restrict__ inter, T* __restrict__ density,
+                     DensityWeights<T> weights, const cx<T>* __restrict__ tw) {
+  SPFFT_LDS_DECL(T);
+  const int B = eng.lines();
+  const int n = eng.n();
+  int tx, ty;
+  block_tile(tx, ty);
+  const int zl = a.zBegin + ty;
+  const int y0 = tx * B;
+  int* xCol = reinterpret_cast<int*>(reinterpret_cast<char*>(lds) + eng.lds_bytes());
+  build_xcol(a, xCol, n);
+  const int yl = min(B, a.Y - y0);
+  T* rho = density + (static_cast<long long>(zl) * a.Y + y0) * n;
+  // inverse x FFT of band `interM`'s tile: rows at out_at(b, x); ends with a barrier
+  auto fft = [&](const cx<T>* interM, const cx<T>* twM) {
+    // per-element arguments pinned in scalar registers (see x_backward_kernel)
+    const int rowStride = pin_uniform(static_cast<int>(a.interStride)), nFreq = pin_uniform(a.nFreq);
+    const int dense = pin_uniform(x_dense(a) ? 1 : 0);
+    auto col_of = [&](int x) { return dense ? (x < nFreq ? x : -1) : xCol[x]; };
+    const cx<T>* src = interM + static_cast<long long>(zl) * a.interZStride + y0;
+    auto load = [&](int b, int pos) -> cx<T> {
+      if (b >= yl) return czero<T>();
+      const int c = col_of(pos);
+      return c < 0 ? czero<T>() : ld_inter(&src[c * rowStride + b]);
+    };
+    eng.global_to_lds(lds, twM, load);
+  };
+  auto row_at = [&](int idx) {
+    const int b = idx / n;
+    return eng.out_at(b, idx - b * n);
+  };
+  if constexpr (!Batched) {
+    fft(inter, tw);
+    density_rows<StreamRho>(lds, rho, weights.w[0], yl * n, row_at);
+  } else {
+    // the per-element arguments (in fft) and the twiddle table are pinned anew
+    // for every band: as loop invariants, the FFT's column offsets and twiddles
+    // were hoisted out of the band loop and stayed live across it (N = 256
+    // fp64: 122 VGPRs with them hoisted, x_backward_kernel 66)
+    auto band_fft = [&](int m) {
+      const cx<T>* twM = reinterpret_cast<const cx<T>*>(pin_uniform64(reinterpret_cast<long long>(tw)));
+      if (m > 0) __syncthreads();  // the previous band's rows have been read
+      fft(static_cast<const cx<T>*>(a.batch.in[m]), twM);
+    };
+    // A full tile of a compile-time engine has a compile-time number of elements
+    // per lane: the bands' contributions are summed in registers and rho is
+    // read and written once, instead of once per band through L2. 256^3 fp64, 8
+    // bands: the call 1692 -> 1600 us (profiles/r8/density).
+    if constexpr (!Eng::kBatchedCopy) {
+      using F = typename Eng::F;
+      constexpr bool kEven = (F::B * Eng::kN) % F::NT == 0;
+      if (kEven && yl == F::B) {
+        constexpr int kIters = kEven ? F::B * Eng::kN / F::NT : 1;
+        T acc[kIters];
+#pragma unroll
+        for (int i = 0; i < kIters; ++i) acc[i] = T(0);
+        for (int m = 0; m < a.batch.count; ++m) {
+          band_fft(m);
+          const T w = weights.w[m];
+#pragma unroll
+          for (int i = 0; i < kIters; ++i)
+            acc[i] = fma(w, norm2(lds[row_at(static_cast<int>(threadIdx.x) + i * F::NT)]), acc[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < kIters; ++i) acc[i] += rho[static_cast<int>(threadIdx.x) + i * F::NT];
+#pragma unroll
+        for (int i = 0; i < kIters; ++i) rho[static_cast<int>(threadIdx.x) + i * F::NT] = acc[i];
+        return;
+      }
+    }
+    for (int m = 0; m < a.batch.count; ++m) {
+      band_fft(m);
+      density_rows<StreamRho>(lds, rho, weights.w[m], yl * n, row_at);
+    }
+  }
+}
+
+// Engines whose batched x density launch keeps the band loop inside the
+// workgroup. The fp32 N = 1024 compile-time engine does not: x_backward_kernel
+// takes 176 VGPRs there, and the values the loop keeps live pushed the kernel
+// into scratch (128 B per lane). Its batches run one single-band launch per
+// band, in order on the stream.
+template <class Eng>
+struct DensityBandLoop {
+  static constexpr bool value = true;
+};
+template <int S, bool LF, bool TwPre>
+struct DensityBandLoop<CtEng<float, 1024, S, LF, TwPre>> {
+  static constexpr bool value = false;
+};
+
+// rho[i] += w |space[i]|^2 in one pass over the space domain (the composed
+// density path: R2C transforms and long x lines): E = cx<T> or T.
+template <typename E, typename T>
+__global__ void __launch_bounds__(256)
+    space_density_kernel(const E* __restrict__ space, T* __restrict__ density, T w, long long count) {
+  const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
+  for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride) {
+    T s2;
+    if constexpr (std::is_same<E, T>::value) {
+      const T s = ld_stream_real(space + i);
+      s2 = s * s;
+    } else {
+      s2 = norm2(ld_stream(space + i));
+    }
+    st_stream_real(density + i, fma(w, s2, ld_stream_real(density + i)));
+  }
+}
+
 // Packed-real x stage (R2C transforms with even dimX): a real row of length n
 // is the complex sequence y[m] = x[2m] + i x[2m+1] of length h = n/2, so one
 // half-length FFT plus a twiddle pre-pass (C2R) or post-pass (R2C) replaces the

@@ -163,5 +163,63 @@ void launch_space_scale(void* space, const T* potential, long long count, bool r
   gpu_check_launch("space_scale", stream);
 }
 
+// Cache policy of the rho accesses of a single-band x density launch: streaming
+// (true) or plain (false); A/B in profiles/r8/density.
+#ifndef SPFFT_DENSITY_STREAM_RHO
+#define SPFFT_DENSITY_STREAM_RHO 1
+#endif
+
+// Fused density x stage (C2C): density += weights[m] |inverse x FFT|^2 over the
+// bands m of the launch, which the workgroups loop over (grid as unbatched).
+template <typename T>
+void launch_x_density(const XArgs& a, const cx<T>* inter, T* density, const T* weights,
+                      const cx<T>* tw, hipStream_t stream) {
+  if (a.L <= a.zBegin || a.Y <= 0) return;
+  const int bands = a.batch.count > 1 ? a.batch.count : 1;
+  DensityWeights<T> w{};
+  for (int m = 0; m < bands && m < kMaxBatch; ++m) w.w[m] = weights[m];
+  with_engine<T, +1, true>(a.n, [&](auto eng, int threads, int lines, std::size_t lds) {
+    using E = decltype(eng);
+    const std::size_t ldsTotal = lds + std::size_t(a.n) * sizeof(int) + 16;
+    const dim3 grid(ceil_div(a.Y, lines), a.L - a.zBegin, 1);
+    auto single = x_density_kernel<E, T, SPFFT_DENSITY_STREAM_RHO != 0, false>;
+    if constexpr (DensityBandLoop<E>::value) {
+      if (bands > 1) {
+        // the bands of a batch revisit the tile of rho: default-policy accesses
+        auto k = x_density_kernel<E, T, false, true>;
+        prepare_kernel(k, ldsTotal);
+        hipLaunchKernelGGL(k, grid, dim3(threads), ldsTotal, stream, eng, a, inter, density, w, tw);
+        gpu_check_launch("x_density", stream);
+        return;
+      }
+    }
+    prepare_kernel(single, ldsTotal);
+    XArgs one = a;
+    one.batch.count = 0;
+    for (int m = 0; m < bands; ++m) {
+      DensityWeights<T> wm{};
+      wm.w[0] = w.w[m];
+      hipLaunchKernelGGL(single, grid, dim3(threads), ldsTotal, stream, eng, one,
+                         bands > 1 ? static_cast<const cx<T>*>(a.batch.in[m]) : inter, density, wm, tw);
+      gpu_check_launch("x_density", stream);
+    }
+  });
+}
+
+// density[i] += weight |space[i]|^2 over `count` elements (complex or, realSpace, real)
+template <typename T>
+void launch_space_density(const void* space, T* density, T weight, long long count, bool realSpace,
+                          hipStream_t stream) {
+  if (count <= 0) return;
+  const unsigned blocks = static_cast<unsigned>(std::min<long long>((count + 255) / 256, 256 * 64));
+  if (realSpace)
+    hipLaunchKernelGGL((space_density_kernel<T, T>), dim3(blocks), dim3(256), 0, stream,
+                       static_cast<const T*>(space), density, weight, count);
+  else
+    hipLaunchKernelGGL((space_density_kernel<cx<T>, T>), dim3(blocks), dim3(256), 0, stream,
+                       static_cast<const cx<T>*>(space), density, weight, count);
+  gpu_check_launch("space_density", stream);
+}
+
 }  // namespace dev
 }  // namespace spfft
