@@ -199,6 +199,36 @@ SPFFT_EXPORT SpfftError spfft_amd_float_multi_transform_accumulate_density(
     int n, SpfftFloatTransform* transforms, const float* const* inputs, const float* weights,
     float* density);
 
+/* Reciprocal-space operator: the space domain f of the transform is replaced by
+ * backward(K * (scale * forward(f))) in one call, exactly what forward(location,
+ * values, scaling), values[i] *= K[i], backward(values, location) give.
+ * kernel holds one entry per local frequency value, in the order of the index
+ * triplets given at transform creation (the order of forward's output): real
+ * (kernelIsComplex = 0) or interleaved complex (kernelIsComplex != 0), double or
+ * float as the transform. values may be NULL; otherwise it receives the scaled
+ * forward values before the multiply (interleaved complex, as forward's
+ * output). kernel and values are host or device pointers. location is where the
+ * space domain is read and where the result is written, as in forward and
+ * backward. scaling is SPFFT_NO_SCALING or SPFFT_FULL_SCALING. Fused plans (GPU
+ * transforms with simple sticks whose z lines fit one workgroup, local or on an
+ * exchange other than *_FLOAT without peer writes) run both z FFTs and the
+ * multiply in one kernel, without a round trip of the values through memory;
+ * other plans run the composition. A null kernel with local elements is
+ * SPFFT_INVALID_PARAMETER_ERROR; the transform stays usable after an error. */
+SPFFT_EXPORT SpfftError spfft_amd_transform_apply_reciprocal(SpfftTransform t,
+                                                             SpfftProcessingUnitType location,
+                                                             const double* kernel,
+                                                             int kernelIsComplex, double* values,
+                                                             SpfftScalingType scaling);
+SPFFT_EXPORT SpfftError spfft_amd_float_transform_apply_reciprocal(SpfftFloatTransform t,
+                                                                   SpfftProcessingUnitType location,
+                                                                   const float* kernel,
+                                                                   int kernelIsComplex, float* values,
+                                                                   SpfftScalingType scaling);
+/* *fused = 1 if the plan runs the fused z stage on the GPU, else 0. */
+SPFFT_EXPORT SpfftError spfft_amd_transform_reciprocal_fused(SpfftTransform t, int* fused);
+SPFFT_EXPORT SpfftError spfft_amd_float_transform_reciprocal_fused(SpfftFloatTransform t, int* fused);
+
 /* Timer tree (SPFFT_TIMING=1 or spfft_amd_timing_enable). enable: 0 off, 1 host
  * scopes only (like the reference's timer), 2 host scopes and GPU stage times
  * (a hipEvent per stage boundary, nodes gpu/<direction>/<stage>). */

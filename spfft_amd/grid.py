@@ -135,6 +135,26 @@ def _density_ptr(rho, prec: _Precision, shape):
     return rho.ctypes.data, rho
 
 
+def _kernel_ptr(k, prec: _Precision, count: int):
+    """Returns (address, keepalive, is_complex) of a reciprocal-space kernel: a real or
+    complex array of the transform's precision with one entry per local value."""
+    if _is_torch(k):
+        if k.dtype not in (prec.torch_real, prec.torch_complex):
+            raise TypeError(f"kernel: expected {prec.torch_real} or {prec.torch_complex}, got {k.dtype}")
+        if k.numel() != count:
+            raise ValueError(f"kernel: expected {count} entries, got {k.numel()}")
+        k = k.contiguous()
+        return k.data_ptr(), k, k.dtype == prec.torch_complex
+    arr = np.asarray(k)
+    if arr.dtype not in (prec.real, prec.complex):
+        raise TypeError(f"kernel: expected {np.dtype(prec.real)} or {np.dtype(prec.complex)}, "
+                        f"got {arr.dtype}")
+    if arr.size != count:
+        raise ValueError(f"kernel: expected {count} entries, got {arr.size}")
+    arr = np.ascontiguousarray(arr)
+    return arr.ctypes.data, arr, arr.dtype == prec.complex
+
+
 class _GridBase:
     _single = False
 
@@ -446,6 +466,56 @@ class _TransformBase:
             v = ctypes.c_int()
             _check(self._prec.amd_fn("transform_density_fused")(self._h, ctypes.byref(v)))
             c = self._cache["density_fused"] = bool(v.value)
+        return c
+
+    def apply_reciprocal(self, kernel, space=None, values=None, location=None,
+                         scaling=Scaling.NONE):
+        """Reciprocal-space operator in one call: the space domain f becomes
+        backward(kernel * forward(f, scaling)).
+
+        `kernel` is a real or complex array (numpy or torch, host or device memory) of
+        the transform's precision with one entry per local frequency value, in the order
+        of the index triplets (the order of forward's output). `space` (optional) is
+        copied into the space domain first. `values` (optional, complex, length
+        num_local_elements) receives the scaled forward values before the multiply.
+        `location` is where the space domain is read and written. Fused plans (see
+        reciprocal_fused) run both z FFTs and the multiply in one kernel. Returns the
+        space-domain view at `location`."""
+        if location is None:
+            location = self.processing_unit
+        kptr, kkeep, cplx = _kernel_ptr(kernel, self._prec, self.num_local_elements)
+        if values is not None:
+            n = values.numel() if _is_torch(values) else np.asarray(values).size
+            if _is_torch(values) and values.dtype != self._prec.torch_complex:
+                raise TypeError(f"values: expected {self._prec.torch_complex}, got {values.dtype}")
+            if not _is_torch(values) and np.asarray(values).dtype != self._prec.complex:
+                raise TypeError(f"values: expected {np.dtype(self._prec.complex)}, "
+                                f"got {np.asarray(values).dtype}")
+            if n != self.num_local_elements:
+                raise ValueError(f"values: expected {self.num_local_elements} entries, got {n}")
+        vptr, vkeep = _data_ptr(values, self._prec, True, "values")
+        if space is not None:
+            dst = self.space_domain(location)
+            if _is_torch(dst):
+                dst.copy_(space if _is_torch(space) else torch.as_tensor(np.asarray(space)))
+            else:
+                src = space.cpu().numpy() if _is_torch(space) else np.asarray(space)
+                np.copyto(dst, src.reshape(dst.shape), casting="same_kind")
+        _check(self._prec.amd_fn("transform_apply_reciprocal")(self._h, int(location), kptr,
+                                                               1 if cplx else 0, vptr, int(scaling)))
+        # asynchronous execution (set_stream(..., synchronous=False)) may still use them
+        self._step_keep = (kkeep, vkeep)
+        return self.space_domain(location)
+
+    @property
+    def reciprocal_fused(self) -> bool:
+        """True if apply_reciprocal runs the fused z stage (GPU, simple sticks, z lines of
+        one workgroup, no *_FLOAT exchange of either precision, no peer-written stick side)."""
+        c = self._cache.get("reciprocal_fused")
+        if c is None:
+            v = ctypes.c_int()
+            _check(self._prec.amd_fn("transform_reciprocal_fused")(self._h, ctypes.byref(v)))
+            c = self._cache["reciprocal_fused"] = bool(v.value)
         return c
 
     # --------------------------------------------------- streams / step API

@@ -159,6 +159,40 @@ class PlaneWaveModel:
                 rho = contrib if rho is None else rho + contrib
         return rho
 
+    def hartree_kernel(self):
+        """K(G) = 4 pi / |G|^2 on the model's plane waves, K(0) = 0 (real, in the
+        transforms' precision, where the transforms run)."""
+        k = getattr(self, "_hartree_kernel", None)
+        if k is None:
+            g2 = self.basis.g2
+            k = np.where(g2 > 0, 4.0 * np.pi / np.where(g2 > 0, g2, 1.0), 0.0)
+            k = k.astype(self.transforms[0]._prec.real)
+            if self.pu == ProcessingUnit.GPU:
+                import torch
+                k = torch.as_tensor(k, device=f"cuda:{self.transforms[0].device_id}")
+            self._hartree_kernel = k
+        return k
+
+    def hartree_potential(self, rho, unfused: bool = False):
+        """V_H(r) = FFT^-1[ 4 pi / |G|^2 * FFT[rho](G) ] on the model's plane waves
+        (the G = 0 term dropped), as a new real array [z][y][x].
+
+        One apply_reciprocal call (on the GPU the z stage multiplies by K(G) in LDS
+        between its two FFTs and the coefficients never go through memory);
+        `unfused` runs the composition forward, K(G) multiply, backward instead."""
+        t = self.transforms[0]
+        k = self.hartree_kernel()
+        if not unfused:
+            v = t.apply_reciprocal(k, space=rho, scaling=Scaling.FULL)
+        else:
+            c = t.forward(space=rho, scaling=Scaling.FULL)
+            if hasattr(c, "mul_"):
+                c.mul_(k)
+            else:
+                c *= k
+            v = t.backward(c)
+        return v.real.clone() if hasattr(v, "clone") else np.array(v.real)
+
     def kinetic(self, psi: Sequence) -> List:
         """T psi_b = |G|^2/2 c_G (diagonal in the plane-wave basis)."""
         g2 = self.basis.g2

@@ -127,6 +127,9 @@ def _prototypes(lib):
         sig[pre + "transform_accumulate_density"] = [V, D, real, D]
         sig[pre + "transform_density_fused"] = [V, c_int_p]
         sig[pre + "multi_transform_accumulate_density"] = [I, c_void_pp, c_void_pp, D, D]
+    for pre in ("spfft_amd_", "spfft_amd_float_"):
+        sig[pre + "transform_apply_reciprocal"] = [V, I, D, I, D, I]
+        sig[pre + "transform_reciprocal_fused"] = [V, c_int_p]
     sig["spfft_amd_timing_enable"] = [I]
     sig["spfft_amd_timing_reset"] = []
     sig["spfft_amd_timing_json"] = [ctypes.c_char_p, ctypes.c_size_t, c_size_t_p]

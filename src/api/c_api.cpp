@@ -605,6 +605,32 @@ SpfftError spfft_amd_float_multi_transform_accumulate_density(int n,
   });
 }
 
+SpfftError spfft_amd_transform_apply_reciprocal(SpfftTransform t, SpfftProcessingUnitType location,
+                                                const double* kernel, int kernelIsComplex,
+                                                double* values, SpfftScalingType scaling) {
+  return with_handle<Transform>(t, [&](Transform& x) {
+    x.impl()->apply_reciprocal(location, kernel, kernelIsComplex != 0, values, scaling);
+  });
+}
+SpfftError spfft_amd_float_transform_apply_reciprocal(SpfftFloatTransform t,
+                                                      SpfftProcessingUnitType location,
+                                                      const float* kernel, int kernelIsComplex,
+                                                      float* values, SpfftScalingType scaling) {
+  return with_handle<TransformFloat>(t, [&](TransformFloat& x) {
+    x.impl()->apply_reciprocal(location, kernel, kernelIsComplex != 0, values, scaling);
+  });
+}
+SpfftError spfft_amd_transform_reciprocal_fused(SpfftTransform t, int* fused) {
+  if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
+  return with_handle<Transform>(
+      t, [&](Transform& x) { *fused = x.impl()->reciprocal_fused() ? 1 : 0; });
+}
+SpfftError spfft_amd_float_transform_reciprocal_fused(SpfftFloatTransform t, int* fused) {
+  if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
+  return with_handle<TransformFloat>(
+      t, [&](TransformFloat& x) { *fused = x.impl()->reciprocal_fused() ? 1 : 0; });
+}
+
 SpfftError spfft_amd_timing_enable(int enable) {
   timing::set_level(enable);
   return SPFFT_SUCCESS;

@@ -1,5 +1,7 @@
 #include "api/transform_impl.hpp"
 
+#include <algorithm>
+
 #include "core/timing.hpp"
 #include "spfft/exceptions.hpp"
 
@@ -164,6 +166,44 @@ void TransformImpl<T>::accumulate_density_xy(T* density, T weight) {
     for (std::size_t i = 0; i < count; ++i)
       density[i] += weight * (space[2 * i] * space[2 * i] + space[2 * i + 1] * space[2 * i + 1]);
   }
+}
+
+template <typename T>
+void TransformImpl<T>::apply_reciprocal(SpfftProcessingUnitType location, const T* kernel,
+                                        bool complexKernel, T* values, SpfftScalingType scaling) {
+  SPFFT_TIMED_SCOPE("apply_reciprocal");
+  if (scaling != SPFFT_NO_SCALING && scaling != SPFFT_FULL_SCALING) throw InvalidParameterError();
+  if (location != SPFFT_PU_HOST && location != SPFFT_PU_GPU) throw InvalidParameterError();
+  if (host_ && location != SPFFT_PU_HOST) throw InvalidParameterError();
+  const std::size_t count = static_cast<std::size_t>(plan_->numLocalElements);
+  if (!kernel && count > 0) throw InvalidParameterError();
+  forward_xy(location);
+  forward_exchange(false);
+  if (gpu_) {
+    gpu_->reciprocal_z(kernel, complexKernel, values, scaling);
+  } else {
+    // host: the plain composition through the frequency values
+    std::vector<T>& work = reciprocalWork_;
+    work.resize(2 * std::max<std::size_t>(count, 1));
+    host_->forward_z(work.data(), scaling);
+    if (values) std::copy(work.begin(), work.begin() + 2 * count, values);
+    if (complexKernel) {
+      for (std::size_t i = 0; i < count; ++i) {
+        const T re = work[2 * i], im = work[2 * i + 1];
+        work[2 * i] = re * kernel[2 * i] - im * kernel[2 * i + 1];
+        work[2 * i + 1] = re * kernel[2 * i + 1] + im * kernel[2 * i];
+      }
+    } else {
+      for (std::size_t i = 0; i < count; ++i) {
+        work[2 * i] *= kernel[i];
+        work[2 * i + 1] *= kernel[i];
+      }
+    }
+    host_->backward_z(work.data());
+  }
+  backward_exchange(false);
+  backward_xy(location);
+  if (gpu_ && gpu_->synchronous()) gpu_->synchronize();
 }
 
 template <typename T>

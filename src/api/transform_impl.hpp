@@ -2,6 +2,7 @@
 #pragma once
 
 #include <memory>
+#include <vector>
 
 #include "api/grid_impl.hpp"
 #include "gpu/gpu_executor.hpp"
@@ -41,6 +42,15 @@ public:
   // the stage behind backward_exchange (multi-transform interleaving)
   void accumulate_density_xy(T* density, T weight);
 
+  // space domain = backward(K * (scale * forward(space domain))) with one real or
+  // complex (interleaved) entry of K per local frequency value, in the order of
+  // the transform's index triplets. `values` (may be NULL) receives the scaled
+  // forward values before the multiply. `location` is where the input space
+  // domain is read and the output space domain is written.
+  void apply_reciprocal(SpfftProcessingUnitType location, const T* kernel, bool complexKernel,
+                        T* values, SpfftScalingType scaling);
+  bool reciprocal_fused() const { return gpu_ && gpu_->reciprocal_fused(); }
+
   void forward_xy(SpfftProcessingUnitType inputLocation);
   void forward_exchange(bool nonBlocking);
   void forward_z(T* output, SpfftScalingType scaling);
@@ -67,6 +77,7 @@ private:
   std::shared_ptr<const IndexPlan> plan_;
   std::unique_ptr<HostExecutor<T>> host_;
   std::unique_ptr<GpuExecutor<T>> gpu_;
+  std::vector<T> reciprocalWork_;  // host apply_reciprocal: the frequency values
 };
 
 }  // namespace spfft

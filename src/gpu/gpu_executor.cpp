@@ -70,6 +70,10 @@ GpuExecutor<T>::GpuExecutor(std::shared_ptr<GridImpl<T>> grid,
   applyFused_ = p.type == SPFFT_TRANS_C2C && !longX_;
   // accumulate_density runs the fused x density stage under the same conditions
   densityFused_ = applyFused_;
+  // apply_reciprocal runs the fused z stage for simple sticks whose z lines fit
+  // one workgroup, on a stick side that is not a *_FLOAT exchange buffer and that
+  // peers do not write (peerWrites_ is known only further down: see below)
+  reciprocalFused_ = p.simpleSticks && !longZ_ && !floatExchange_;
   // Backward z -> y hand-off through the Infinity Cache: a single rank's z
   // stage writes the stick array that its y stage reads next. With the default
   // cache policy on both sides (instead of streaming) and a stick array that
@@ -131,6 +135,7 @@ GpuExecutor<T>::GpuExecutor(std::shared_ptr<GridImpl<T>> grid,
     }
     // collective data-plane setup happens at plan time
     peerWrites_ = grid_->device_comm().peer_writes();
+    if (peerWrites_) reciprocalFused_ = false;  // forward and backward address the stick side differently
     if (peerWrites_) {
       peerStickStride_ = p.dimZ + aligned_row_pad(p.dimZ, stickElemBytes);
       if (static_cast<i64>(p.local_sticks()) * peerStickStride_ > grid_->slot_elements(GridImpl<T>::kStickSide))
@@ -224,7 +229,7 @@ void GpuExecutor<T>::log_plan() const {
   if (p.size > 1) plane = const_cast<GridImpl<T>&>(*grid_).device_comm().describe();
   std::fprintf(stderr,
                "spfft[gpu rank %d/%d] %dx%dx%d %s %s: sticks=%d planes=%d columns=%d | z{%s} "
-               "y{%s} x{%s}%s inter_planes=%d apply_local=%s density=%s | exchange=%s%s plane=%s chunks=%d stick_blocks=%d "
+               "y{%s} x{%s}%s inter_planes=%d apply_local=%s density=%s reciprocal=%s | exchange=%s%s plane=%s chunks=%d stick_blocks=%d "
                "steps=%zu+%zu (%.2f MB per peer) peer_writes=%d peer_offsets=[%lld, %lld] "
                "library_streams=%d\n",
                p.rank, p.size, p.dimX, p.dimY, p.dimZ,
@@ -233,7 +238,7 @@ void GpuExecutor<T>::log_plan() const {
                describe(longZ_, lpZ_, p.dimZ, false).c_str(), describe(longY_, lpY_, p.dimY, true).c_str(),
                describe(longX_, lpX_, twXh_ ? p.dimX / 2 : p.dimX, true).c_str(),
                twXh_ ? " packed-real" : "", interPlanes_, applyFused_ ? "fused" : "unfused",
-               densityFused_ ? "fused" : "composed",
+               densityFused_ ? "fused" : "composed", reciprocalFused_ ? "fused" : "composed",
                layout_.buffered ? "buffered" : "compact",
                floatExchange_ ? "-float" : "", plane.c_str(), exchChunks_, stickBlocks_, bwdSteps_.size(),
                fwdSteps_.size(), chunkModel_ / 1e6, peerWrites_ ? 1 : 0, peerOffsetRange_[0],
@@ -1288,6 +1293,74 @@ void GpuExecutor<T>::forward_z(T* output, SpfftScalingType scaling) {
                              hipMemcpyDeviceToHost, stream_),
               "hipMemcpyAsync");
   }
+}
+
+// -------------------------------------------------- reciprocal-space operator
+// apply_reciprocal = forward_xy, forward_exchange, reciprocal_z,
+// backward_exchange, backward_xy (TransformImpl::apply_reciprocal). Fused plans
+// run one z stage in place on the stick side, which forward and backward
+// address with the same zargs(): per stick block it waits for the block's
+// arrival (blockEv_), transforms, multiplies and transforms back, and records
+// the event its backward messages wait for (zEv_). Other plans compose forward_z
+// into a device work buffer, a multiply of the sparse values and backward_z.
+template <typename T>
+void GpuExecutor<T>::reciprocal_z(const T* kernel, bool complexKernel, T* values,
+                                  SpfftScalingType scaling) {
+  SPFFT_TIMED_SCOPE("gpu_reciprocal_z");
+  DeviceGuard guard(deviceId_);
+  const IndexPlan& p = *plan_;
+  const std::size_t count = static_cast<std::size_t>(p.numLocalElements);
+  if (count > 0 && !kernel) throw InvalidParameterError();
+  const T* kern = kernel;
+  if (count > 0 && !is_device_pointer(kernel)) {
+    const std::size_t bytes = count * (complexKernel ? sizeof(cx<T>) : sizeof(T));
+    if (!recKernel_ || recKernel_->bytes() < bytes) recKernel_.reset(new DeviceBuffer(bytes));
+    gpu_check(hipMemcpyAsync(recKernel_->data<T>(), kernel, bytes, hipMemcpyHostToDevice, stream_),
+              "hipMemcpyAsync");
+    kern = recKernel_->data<T>();
+  }
+  // the staging buffer: forward_z and backward_z get device pointers and leave it alone
+  auto work = [&]() { return staging(count); };
+  const bool hostValues = values && count > 0 && !is_device_pointer(values);
+  auto download = [&](const cx<T>* src) {
+    gpu_check(hipMemcpyAsync(values, src, sizeof(cx<T>) * count, hipMemcpyDeviceToHost, stream_),
+              "hipMemcpyAsync");
+  };
+  if (!reciprocalFused_) {
+    // forward values into the caller's device array or the work buffer; the
+    // product goes to the work buffer, which backward_z reads
+    cx<T>* fv = values && !hostValues ? reinterpret_cast<cx<T>*>(values) : work();
+    forward_z(reinterpret_cast<T*>(fv), scaling);
+    if (hostValues) download(fv);
+    cx<T>* prod = work();
+    dev::launch_values_scale<T>(prod, fv, kern, complexKernel, static_cast<long long>(count), stream_);
+    stage_mark("forward", "multiply");
+    backward_z(reinterpret_cast<const T*>(prod));
+    return;
+  }
+  {
+    StageEnd stageEnd{this, "forward", "z_reciprocal"};
+    const T factor = scaling == SPFFT_FULL_SCALING
+                         ? static_cast<T>(1.0 / (static_cast<double>(p.dimX) * p.dimY * p.dimZ))
+                         : T(1);
+    cx<T>* out = !values ? nullptr : hostValues ? work() : reinterpret_cast<cx<T>*>(values);
+    auto* stick = static_cast<cx<T>*>(grid_->device_slot(GridImpl<T>::kStickSide));
+    auto a = zargs();
+    a.plainSticks = plainHandoff_;
+    const int I = pipelined() ? stickBlocks_ : 1;
+    for (int i = 0; i < I; ++i) {
+      if (pipelined()) {
+        blockEv_[i]->wait_on(stream_);  // stick block i has arrived
+        a.stickBegin = stickBounds_[i];
+        a.numSticks = stickBounds_[i + 1];
+      }
+      dev::launch_z_reciprocal<T>(a, stick, kern, complexKernel, out, factor, twZ_->data<cx<T>>(), stream_);
+      if (pipelined()) zEv_[i]->record(stream_);  // its backward messages may leave
+    }
+    if (hostValues) download(out);
+  }
+  // the backward exchange and y/x stages follow: their marks belong to "backward"
+  stage_mark("backward", nullptr);
 }
 
 // -------------------------------------------------------------- local operator

@@ -92,6 +92,19 @@ public:
                                        const std::vector<T>& weights, T* density,
                                        GpuExecutor* after = nullptr);
 
+  // Reciprocal-space operator (TransformImpl::apply_reciprocal): the stage
+  // between forward_exchange and backward_exchange. Fused plans (simple sticks,
+  // z lines of one workgroup, no *_FLOAT exchange, stick side not written by
+  // peers) run one z stage in place on the stick side: forward z
+  // FFT, multiply by the kernel, inverse z FFT in LDS; the sparse values are
+  // only written when `values` is given. Other plans run forward_z into the
+  // caller's device `values` or the staging buffer, a multiply of the values
+  // into the staging buffer and backward_z. `kernel` (one real or
+  // complex entry per local value) and `values` (NULL, or the scaled forward
+  // values) are host or device pointers.
+  void reciprocal_z(const T* kernel, bool complexKernel, T* values, SpfftScalingType scaling);
+  bool reciprocal_fused() const { return reciprocalFused_; }
+
   void synchronize();
   bool synchronous() const { return synchronous_; }
   // Execute on `stream` (nullptr = the legacy default stream); work is then
@@ -131,6 +144,8 @@ private:
   bool densityFused_ = false;
   void order_after_density(GpuExecutor* prev);  // this stream waits for prev's work so far
   std::unique_ptr<GpuEvent> densityEvent_;
+  bool reciprocalFused_ = false;
+  std::unique_ptr<DeviceBuffer> recKernel_;  // stages a host kernel
   struct GraphEntry {
     int dir;  // 0 backward, 1 forward
     const void* in;

@@ -124,6 +124,18 @@ void launch_z_backward(const ZArgs& a, const cx<T>* values, BT* out, const cx<T>
 template <typename T, typename BT>
 void launch_z_forward(const ZArgs& a, const BT* in, cx<T>* values, T scale, const cx<T>* tw,
                       hipStream_t stream);
+// Fused reciprocal-space operator z stage, in place on the stick side (simple
+// sticks: ZArgs::desc non-null): forward z FFT, values[i] = scale * coefficient
+// (when `values` is non-null), coefficient *= kernel[i] on the sparse set and
+// zero elsewhere, hermitian fill of the (0,0) stick, inverse z FFT. `kernel`
+// has one entry per value, real or (complexKernel) interleaved complex.
+template <typename T>
+void launch_z_reciprocal(const ZArgs& a, cx<T>* sticks, const T* kernel, bool complexKernel,
+                         cx<T>* values, T scale, const cx<T>* tw, hipStream_t stream);
+// out[i] = in[i] * kernel[i] over sparse values (composed path; out may be in).
+template <typename T>
+void launch_values_scale(cx<T>* out, const cx<T>* in, const T* kernel, bool complexKernel, long long count,
+                         hipStream_t stream);
 template <typename T, typename BT>
 void launch_y_backward(const YArgs& a, const BT* in, cx<T>* inter, const cx<T>* tw,
                        hipStream_t stream);

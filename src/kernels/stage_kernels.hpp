@@ -375,7 +375,7 @@ __device__ __forceinline__ cx<T> czero() {
 // (src/symmetry/gpu_kernels/symmetry_kernels.cu:56-78, 119-141) as two
 // barrier-separated phases of one workgroup.
 template <class Eng, typename T>
-__device__ void hermitian_lines(const Eng& eng, cx<T>* lds, int b0, int count, int n) {
+__device__ __forceinline__ void hermitian_lines_inline(const Eng& eng, cx<T>* lds, int b0, int count, int n) {
   const int h1 = n / 2;          // k in [1, n/2]
   const int h2 = n - 1 - h1;     // k in [n/2+1, n-1]
   for (int idx = threadIdx.x; idx < count * h1; idx += blockDim.x) {
@@ -390,6 +390,14 @@ __device__ void hermitian_lines(const Eng& eng, cx<T>* lds, int b0, int count, i
     if (nonzero(v)) lds[eng.in_at(b, n - k)] = conj(v);
   }
   __syncthreads();
+}
+
+// Out of line where the compiler decides so (the stage kernels); the fused
+// reciprocal z stage inlines the body: a call would pass its engine, a run-time
+// plan, through scratch memory.
+template <class Eng, typename T>
+__device__ void hermitian_lines(const Eng& eng, cx<T>* lds, int b0, int count, int n) {
+  hermitian_lines_inline(eng, lds, b0, count, n);
 }
 
 template <typename T>
@@ -629,6 +637,17 @@ struct ZSeg {
     if (single == 0) {
       long long* t = reinterpret_cast<long long*>(ldsTab);
       for (int i = threadIdx.x; i < 2 * n; i += blockDim.x) t[i] = a.zTab[i];
+      __syncthreads();
+    }
+  }
+  // the same from the fields alone, always inlined (a call would pass ZArgs
+  // through scratch memory: the fused reciprocal z stage)
+  __device__ __forceinline__ ZSeg(int single_, long long stride_, const long long* zTab, char* ldsTab, int n)
+      : single(pin_uniform(single_)), stride(pin_uniform64(stride_)),
+        tab(reinterpret_cast<const long long*>(ldsTab)), gtab(zTab) {
+    if (single == 0) {
+      long long* t = reinterpret_cast<long long*>(ldsTab);
+      for (int i = threadIdx.x; i < 2 * n; i += blockDim.x) t[i] = zTab[i];
       __syncthreads();
     }
   }
@@ -1399,6 +1418,105 @@ __global__ void __launch_bounds__(256)
       st_stream_real(space + i, ld_stream_real(space + i) * w);
     else
       st_stream(space + i, scale(ld_stream(space + i), w));
+  }
+}
+
+// Fused reciprocal-space operator z stage (simple sticks): forward z FFT of the
+// block's sticks into LDS, values = scale * coefficient and coefficient *= K on
+// the sparse set (zero elsewhere), (0,0)-stick hermitian fill, inverse z FFT,
+// store to the same stick addresses; the sparse values make no round trip
+// through memory. `fwd` is forward_twin(eng): the forward engine on the LDS
+// lines of the backward stage's engine `eng`.
+//
+// The multiply walks the B x n LDS elements with z fastest, so a wave's lanes
+// follow the z-runs of a stick: consecutive value indices, coalesced loads of K
+// and stores of `values`. kApplyUnroll loads of K are in flight per lane. No LDS
+// race: lane idx reads fwd.out_at and writes eng.in_at of its own element,
+// which are the same slot (compile-time engines on one layout, in-place run-time
+// plans, Bluestein) or slots of two disjoint regions (ping-pong run-time plans
+// with an odd pass count), as in scale_rows.
+//
+// In place on the stick side. Invariant that makes it safe: the forward FFT has
+// loaded every element of the block's sticks before the inverse FFT stores any
+// (barriers in between), and no other workgroup touches these sticks.
+template <typename T, bool Cplx>
+__device__ __forceinline__ cx<T> ld_kernel(const T* __restrict__ k, long long i) {
+  if constexpr (Cplx) return ld_stream(reinterpret_cast<const cx<T>*>(k) + i);
+  else return mk<T>(ld_stream_real(k + i), T(0));
+}
+
+template <class Eng, class Fwd, typename T, bool Cplx, bool Plain>
+__global__ void __launch_bounds__(Eng::kBlock)
+    z_reciprocal_kernel(Eng eng, Fwd fwd, ZArgs a, cx<T>* sticks, const T* __restrict__ kern,
+                        cx<T>* __restrict__ values, T scale, const cx<T>* __restrict__ tw) {
+  SPFFT_LDS_DECL(T);
+  const int B = eng.lines();
+  const int n = eng.n();
+  const int s0 = a.stickBegin + block_tile_x() * B;
+  const int nl = min(B, a.numSticks - s0);
+  const ZSeg seg(a.single, a.stickStride, a.zTab,
+                 reinterpret_cast<char*>(lds) + zseg_lds_offset(eng.lds_bytes(), B), n);
+  StickDesc* d = reinterpret_cast<StickDesc*>(reinterpret_cast<char*>(lds) + eng.lds_bytes());
+  for (int b = threadIdx.x; b < nl; b += blockDim.x) d[b] = a.desc[s0 + b];
+  // result at fwd.out_at(b, z); ends with a barrier (which also publishes d)
+  fwd.global_to_lds(lds, tw, [&](int b, int pos) -> cx<T> {
+    if (b >= nl) return czero<T>();
+    return ld_stream(&sticks[seg.at(s0 + b, pos)]);
+  });
+  const bool keep = pin_uniform(values != nullptr ? 1 : 0) != 0;
+  const int total = B * n;
+  for (int base = threadIdx.x; base < total; base += blockDim.x * kApplyUnroll) {
+    cx<T> w[kApplyUnroll];
+    int vi[kApplyUnroll];
+#pragma unroll
+    for (int u = 0; u < kApplyUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      vi[u] = -1;
+      if (idx < total) {
+        const int b = idx / n, z = idx - b * n;
+        if (b < nl) {
+          const StickDesc& q = d[b];
+          const int j = desc_offset(q, z);
+          if (j >= 0) {
+            vi[u] = q.valueStart + j;
+            w[u] = ld_kernel<T, Cplx>(kern, vi[u]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kApplyUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        const int b = idx / n, z = idx - b * n;
+        cx<T> r = czero<T>();
+        if (vi[u] >= 0) {
+          const cx<T> v = spfft::scale(lds[fwd.out_at(b, z)], scale);
+          if (keep) st_values(&values[vi[u]], v);
+          if constexpr (Cplx) r = cmul(v, w[u]);
+          else r = spfft::scale(v, w[u].x);
+        }
+        lds[eng.in_at(b, z)] = r;
+      }
+    }
+  }
+  __syncthreads();
+  if (a.zeroStick >= s0 && a.zeroStick < s0 + nl) hermitian_lines_inline(eng, lds, a.zeroStick - s0, 1, n);
+  eng.lds_to_global(lds, tw, [&](int b, int pos, cx<T> v) {
+    if (b < nl) st_stick<Plain>(&sticks[seg.at(s0 + b, pos)], v);
+  });
+}
+
+// out[i] = in[i] * K[i] over `count` sparse values (the composed reciprocal-space
+// operator path; out may be in); K real or complex.
+template <typename T, bool Cplx>
+__global__ void __launch_bounds__(256)
+    values_scale_kernel(cx<T>* out, const cx<T>* in, const T* __restrict__ kern, long long count) {
+  const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
+  for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride) {
+    const cx<T> w = ld_kernel<T, Cplx>(kern, i);
+    if constexpr (Cplx) out[i] = cmul(in[i], w);
+    else out[i] = spfft::scale(in[i], w.x);
   }
 }
 

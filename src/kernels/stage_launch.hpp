@@ -50,6 +50,42 @@ void launch_z_forward(const ZArgs& a, const BT* in, cx<T>* values, T scale, cons
   });
 }
 
+// Fused reciprocal-space operator z stage (simple sticks, in place on the stick
+// side). The forward and the inverse engine share the backward stage's shape
+// (forward_twin), so the launch takes the LDS and grid of launch_z_backward.
+template <typename T>
+void launch_z_reciprocal(const ZArgs& a, cx<T>* sticks, const T* kernel, bool complexKernel,
+                         cx<T>* values, T scale, const cx<T>* tw, hipStream_t stream) {
+  if (a.numSticks <= a.stickBegin) return;
+  with_engine<T, +1>(a.n, [&](auto eng, int threads, int lines, std::size_t lds) {
+    auto fwd = forward_twin(eng);
+    using E = decltype(eng);
+    using F = decltype(fwd);
+    const bool plain = a.plainSticks != 0;
+    auto k = complexKernel ? (plain ? z_reciprocal_kernel<E, F, T, true, true> : z_reciprocal_kernel<E, F, T, true, false>)
+                           : (plain ? z_reciprocal_kernel<E, F, T, false, true> : z_reciprocal_kernel<E, F, T, false, false>);
+    std::size_t ldsTotal = 0;
+    const ZArgs b = z_args_for_lds(a, lds, lines, &ldsTotal);
+    prepare_kernel(k, ldsTotal);
+    hipLaunchKernelGGL(k, dim3(ceil_div(a.numSticks - a.stickBegin, lines)), dim3(threads), ldsTotal, stream,
+                       eng, fwd, b, sticks, kernel, values, scale, tw);
+    gpu_check_launch("z_reciprocal", stream);
+  });
+}
+
+// out[i] = in[i] * kernel[i] over `count` sparse values (composed path; out may be in)
+template <typename T>
+void launch_values_scale(cx<T>* out, const cx<T>* in, const T* kernel, bool complexKernel, long long count,
+                         hipStream_t stream) {
+  if (count <= 0) return;
+  const unsigned blocks = static_cast<unsigned>(std::min<long long>((count + 255) / 256, 256 * 64));
+  if (complexKernel)
+    hipLaunchKernelGGL((values_scale_kernel<T, true>), dim3(blocks), dim3(256), 0, stream, out, in, kernel, count);
+  else
+    hipLaunchKernelGGL((values_scale_kernel<T, false>), dim3(blocks), dim3(256), 0, stream, out, in, kernel, count);
+  gpu_check_launch("values_scale", stream);
+}
+
 template <typename T, typename BT>
 void launch_y_backward(const YArgs& a, const BT* in, cx<T>* inter, const cx<T>* tw,
                        hipStream_t stream) {

@@ -7,7 +7,11 @@ bands per multi_transform call). Prints one JSON line.
 --unfused times the composition backward, V(r) multiply, forward instead of the
 fused apply_local; --op density times PlaneWaveModel.density, rho = sum_b w_b
 |psi_b|^2 with one accumulate_density per band, and with --unfused today's
-composition of backward and torch passes.)
+composition of backward and torch passes; --op hartree times
+PlaneWaveModel.hartree_potential, one apply_reciprocal per call, against its
+composition forward, K(G) multiply, backward in alternating rounds of one
+process, and prints the GPU stage times of both and the modelled bytes of the two
+z stages; with --r2c on an R2C transform.)
 """
 import argparse
 import json
@@ -26,10 +30,12 @@ def main():
     ap.add_argument("--transforms", type=int, default=8)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--unfused", action="store_true")
-    ap.add_argument("--op", choices=("local", "density"), default="local")
+    ap.add_argument("--op", choices=("local", "density", "hartree"), default="local")
     ap.add_argument("--grid", type=int, default=0,
                     help="FFT grid N^3 instead of the density grid of the cutoff (the cutoff "
                          "sphere may then reach N/2, the transforms' own minimum grid)")
+    ap.add_argument("--r2c", action="store_true",
+                    help="--op hartree on an R2C transform (hermitian half of the sphere)")
     a = ap.parse_args()
     import torch
 
@@ -45,6 +51,9 @@ def main():
            for _ in range(a.bands)]
     nx, ny, nz = basis.fft_dims
     v_r = torch.rand((nz, ny, nx), dtype=torch.float64, device=dev, generator=g)
+    if a.op == "hartree":
+        hartree(a, basis, model, v_r)  # (a real field stands in for rho)
+        return
     if a.op == "density":
         weights = [1.0 + 0.01 * b for b in range(a.bands)]
 
@@ -73,6 +82,94 @@ def main():
                       "path": "unfused" if a.unfused else "apply_local",
                       "bands_per_s": a.bands * a.reps / dt,
                       "transforms_per_s": 2 * a.bands * a.reps / dt}), flush=True)
+
+
+def _gpu_stage_medians(tree):
+    """gpu/<direction>/<stage> -> median seconds, from the native timing tree."""
+    out = {}
+    for n in tree["timings"]:
+        if n["identifier"] != "gpu":
+            continue
+        for d in n["sub-timings"]:
+            for st in d["sub-timings"]:
+                out[d["identifier"] + "/" + st["identifier"]] = st["median"]
+    return out
+
+
+def hartree(a, basis, model, rho):
+    """Fused and composed calls in alternating rounds of one process (medians over the
+    rounds), then the GPU stage times of each variant from the timing tree. --r2c runs
+    the same operator on an R2C transform over the hermitian half of the model's sphere
+    (the hermitian fill of the (0,0) stick runs inside the fused kernel)."""
+    import numpy as np
+    import torch
+
+    import spfft_amd as sp
+    nx, ny, nz = basis.fft_dims
+    if a.r2c:
+        idx = basis.indices
+        # the half the R2C transform takes: x >= 0, and of the x = 0 plane y >= 0 (of the
+        # (0,0) stick z >= 0)
+        keep = (idx[:, 0] > 0) | ((idx[:, 0] == 0) & ((idx[:, 1] > 0) |
+                                                     ((idx[:, 1] == 0) & (idx[:, 2] >= 0))))
+        idx, g2 = np.ascontiguousarray(idx[keep]), basis.g2[keep]
+        grid = sp.Grid(nx, ny, nz, nx * ny, sp.ProcessingUnit.GPU, 1)
+        t = grid.create_transform(sp.ProcessingUnit.GPU, sp.TransformType.R2C, nx, ny, nz, nz, idx)
+        k = torch.as_tensor(np.where(g2 > 0, 4 * np.pi / np.where(g2 > 0, g2, 1.0), 0.0), device="cuda")
+
+        def call(unfused):
+            if not unfused:
+                return t.apply_reciprocal(k, space=rho, scaling=sp.Scaling.FULL).clone()
+            c = t.forward(space=rho, scaling=sp.Scaling.FULL)
+            c.mul_(k)
+            return t.backward(c).clone()
+    else:
+        idx = basis.indices
+        t = model.transforms[0]
+
+        def call(unfused):
+            return model.hartree_potential(rho, unfused=unfused)
+    rounds, calls = max(3, a.reps), 20
+    times = {"fused": [], "composed": []}
+    for unfused in (False, True):
+        call(unfused)
+    for _ in range(rounds):
+        for name, unfused in (("fused", False), ("composed", True)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                call(unfused)
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / calls)
+    med = {k_: sorted(v)[len(v) // 2] for k_, v in times.items()}
+    stages = {}
+    for name, unfused in (("fused", False), ("composed", True)):
+        sp.timing_reset()
+        sp.timing_enable(True)
+        try:
+            for _ in range(calls):
+                call(unfused)
+            t.synchronize()
+            torch.cuda.synchronize()
+            stages[name] = _gpu_stage_medians(sp.timing_json())
+        finally:
+            sp.timing_enable(False)
+    key = idx[:, 0].astype("int64") * (2 * ny + 1) + idx[:, 1]
+    sticks = len(set(key.tolist()))
+    stick_bytes, value_bytes = sticks * nz * 16, len(idx) * 16
+    # z stages only: composed reads and writes the sticks and the values once per
+    # direction and multiplies the values in between (with a real K);
+    # fused reads and writes the sticks once and reads K
+    print(json.dumps({"workload": "plane-wave Hartree potential", "type": "r2c" if a.r2c else "c2c",
+                      "fft_dims": list(basis.fft_dims),
+                      "num_values": len(idx), "sticks": sticks,
+                      "reciprocal_fused": t.reciprocal_fused,
+                      "calls_per_s": {k_: 1.0 / v for k_, v in med.items()},
+                      "min_s": {k_: min(v) for k_, v in times.items()},
+                      "ratio_composed_over_fused": med["composed"] / med["fused"],
+                      "gpu_stage_median_s": stages,
+                      "model_z_bytes": {"composed": 2 * stick_bytes + 4 * value_bytes + value_bytes // 2,
+                                        "fused": 2 * stick_bytes + value_bytes // 2}}), flush=True)
 
 
 if __name__ == "__main__":
