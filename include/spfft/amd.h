@@ -229,6 +229,39 @@ SPFFT_EXPORT SpfftError spfft_amd_float_transform_apply_reciprocal(SpfftFloatTra
 SPFFT_EXPORT SpfftError spfft_amd_transform_reciprocal_fused(SpfftTransform t, int* fused);
 SPFFT_EXPORT SpfftError spfft_amd_float_transform_reciprocal_fused(SpfftFloatTransform t, int* fused);
 
+/* Exchange (Fock) pair operator of hybrid functionals in one call:
+ *   acc += weight * a * backward(K * (scale * forward(conj(a) * b)))
+ * a, b and acc cover the local space domain [localZ][dimY][dimX]: interleaved
+ * complex for C2C transforms, real for R2C (conj is then the identity and the
+ * update is real); double or float as the transform. kernel (one real or
+ * interleaved complex entry per local frequency value) and values (NULL, or the
+ * scaled forward values c(G) before the multiply) are as in
+ * spfft_amd_transform_apply_reciprocal. All pointers are host or device
+ * pointers; host arrays of a GPU transform are staged on its stream. a == b is
+ * allowed, acc overlapping a or b is undefined; a and b are not modified.
+ * scaling is SPFFT_NO_SCALING or SPFFT_FULL_SCALING. After the call the contents
+ * of the space domain are unspecified: fused plans (GPU C2C transforms whose x
+ * lines fit one workgroup) form the pair density in the forward x stage's loads
+ * and accumulate from the backward x stage's LDS, never form the space domain
+ * and leave it untouched; other plans (R2C, long x lines, host) pass through
+ * it. The z stage is the one of apply_reciprocal. Collective on distributed
+ * grids. A null a, b or acc with local planes, or a null kernel with local
+ * values, is SPFFT_INVALID_PARAMETER_ERROR; the transform stays usable. */
+SPFFT_EXPORT SpfftError spfft_amd_transform_accumulate_fock(SpfftTransform t, const double* a,
+                                                            const double* b, const double* kernel,
+                                                            int kernelIsComplex, double weight,
+                                                            double* acc, double* values,
+                                                            SpfftScalingType scaling);
+SPFFT_EXPORT SpfftError spfft_amd_float_transform_accumulate_fock(SpfftFloatTransform t,
+                                                                  const float* a, const float* b,
+                                                                  const float* kernel,
+                                                                  int kernelIsComplex, float weight,
+                                                                  float* acc, float* values,
+                                                                  SpfftScalingType scaling);
+/* *fused = 1 if the plan runs the fused pair x stages on the GPU, else 0. */
+SPFFT_EXPORT SpfftError spfft_amd_transform_fock_fused(SpfftTransform t, int* fused);
+SPFFT_EXPORT SpfftError spfft_amd_float_transform_fock_fused(SpfftFloatTransform t, int* fused);
+
 /* Timer tree (SPFFT_TIMING=1 or spfft_amd_timing_enable). enable: 0 off, 1 host
  * scopes only (like the reference's timer), 2 host scopes and GPU stage times
  * (a hipEvent per stage boundary, nodes gpu/<direction>/<stage>). */

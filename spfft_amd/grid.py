@@ -155,6 +155,33 @@ def _kernel_ptr(k, prec: _Precision, count: int):
     return arr.ctypes.data, arr, arr.dtype == prec.complex
 
 
+def _space_array_ptr(x, prec: _Precision, shape, real: bool, what: str, writable: bool):
+    """Returns (address, keepalive) of an array over the space domain: shape `shape`,
+    complex (real for R2C) in the transform's precision. A wrong dtype is a TypeError, a
+    wrong shape a ValueError; an array that is written is never copied."""
+    if _is_torch(x):
+        want = prec.torch_real if real else prec.torch_complex
+        if x.dtype != want:
+            raise TypeError(f"{what}: expected {want}, got {x.dtype}")
+        if tuple(x.shape) != tuple(shape):
+            raise ValueError(f"{what}: expected shape {tuple(shape)}, got {tuple(x.shape)}")
+        if not x.is_contiguous():
+            if writable:
+                raise ValueError(f"{what} must be contiguous")
+            x = x.contiguous()
+        return x.data_ptr(), x
+    want = np.dtype(prec.real if real else prec.complex)
+    if not isinstance(x, np.ndarray) or x.dtype != want:
+        raise TypeError(f"{what}: expected a {want} array, got "
+                        f"{getattr(x, 'dtype', type(x).__name__)}")
+    if tuple(x.shape) != tuple(shape):
+        raise ValueError(f"{what}: expected shape {tuple(shape)}, got {tuple(x.shape)}")
+    if writable and (not x.flags.c_contiguous or not x.flags.writeable):
+        raise ValueError(f"{what} must be a writable C-contiguous array")
+    x = np.ascontiguousarray(x)
+    return x.ctypes.data, x
+
+
 class _GridBase:
     _single = False
 
@@ -516,6 +543,56 @@ class _TransformBase:
             v = ctypes.c_int()
             _check(self._prec.amd_fn("transform_reciprocal_fused")(self._h, ctypes.byref(v)))
             c = self._cache["reciprocal_fused"] = bool(v.value)
+        return c
+
+    def accumulate_fock(self, a, b, kernel, weight, acc, values=None, scaling=Scaling.NONE):
+        """Exchange (Fock) pair operator in one call:
+        acc += weight * a * backward(kernel * forward(conj(a) * b, scaling)).
+
+        `a`, `b` and `acc` are arrays (numpy or torch, host or device memory) of shape
+        space_domain_shape() in the transform's precision: complex for C2C, real for R2C
+        (conj is then the identity). `a` and `b` are not modified and may be the same
+        array; `acc` is updated in place, never copied, and must not overlap them.
+        `kernel` and `values` are as in apply_reciprocal; `values` receives the scaled
+        forward values c(G) of the pair density. The contents of the space domain are
+        unspecified afterwards; fused plans (see fock_fused) never form it and leave it
+        untouched. Returns `acc`."""
+        shape = self.space_domain_shape()
+        real = self.type == TransformType.R2C
+        aptr, akeep = _space_array_ptr(a, self._prec, shape, real, "a", False)
+        if b is a:
+            bptr, bkeep = aptr, akeep
+        else:
+            bptr, bkeep = _space_array_ptr(b, self._prec, shape, real, "b", False)
+        cptr, ckeep = _space_array_ptr(acc, self._prec, shape, real, "acc", True)
+        kptr, kkeep, cplx = _kernel_ptr(kernel, self._prec, self.num_local_elements)
+        if values is not None:
+            n = values.numel() if _is_torch(values) else np.asarray(values).size
+            if _is_torch(values) and values.dtype != self._prec.torch_complex:
+                raise TypeError(f"values: expected {self._prec.torch_complex}, got {values.dtype}")
+            if not _is_torch(values) and np.asarray(values).dtype != self._prec.complex:
+                raise TypeError(f"values: expected {np.dtype(self._prec.complex)}, "
+                                f"got {np.asarray(values).dtype}")
+            if n != self.num_local_elements:
+                raise ValueError(f"values: expected {self.num_local_elements} entries, got {n}")
+        vptr, vkeep = _data_ptr(values, self._prec, True, "values")
+        if Scaling(scaling) not in (Scaling.NONE, Scaling.FULL):
+            raise ValueError(f"scaling: expected Scaling.NONE or Scaling.FULL, got {scaling}")
+        _check(self._prec.amd_fn("transform_accumulate_fock")(
+            self._h, aptr, bptr, kptr, 1 if cplx else 0, float(weight), cptr, vptr, int(scaling)))
+        # asynchronous execution (set_stream(..., synchronous=False)) may still use them
+        self._step_keep = (akeep, bkeep, kkeep, ckeep, vkeep)
+        return acc
+
+    @property
+    def fock_fused(self) -> bool:
+        """True if accumulate_fock runs the fused pair x stages (GPU, C2C, x lines of one
+        workgroup); its z stage follows reciprocal_fused."""
+        c = self._cache.get("fock_fused")
+        if c is None:
+            v = ctypes.c_int()
+            _check(self._prec.amd_fn("transform_fock_fused")(self._h, ctypes.byref(v)))
+            c = self._cache["fock_fused"] = bool(v.value)
         return c
 
     # --------------------------------------------------- streams / step API

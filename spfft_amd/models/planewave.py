@@ -9,6 +9,11 @@ per band are:
     backward transform, pointwise multiply in real space, forward transform;
   * density accumulation, rho(r) = sum_b w_b |psi_b(r)|^2: backward transforms.
 
+Hybrid functionals add the exact-exchange operator, whose cost grows with the
+square of the number of occupied bands: per pair (a, b) a forward transform of
+conj(psi_a) psi_b, a multiply by K(G) and a backward transform, accumulated with
+psi_a (exchange_operator, one accumulate_fock call per pair).
+
 Both run fully on the GPU with the space domain kept resident in the Grid's HBM
 slab, several bands at once through multi_transform.
 
@@ -192,6 +197,91 @@ class PlaneWaveModel:
                 c *= k
             v = t.backward(c)
         return v.real.clone() if hasattr(v, "clone") else np.array(v.real)
+
+    def _exchange_setup(self):
+        """The transform of the exchange operator, built on first use: the pair densities
+        conj(psi_a) psi_b hold |G| <= 2 Gmax, so its index set is the sphere |G|^2/2 <=
+        4 ecut (clipped to the FFT grid), with K(G) = 4 pi / |G|^2 and K(0) = 0."""
+        if getattr(self, "_exchange", None) is not None:
+            return self._exchange
+        b = self.basis
+        dims = b.fft_dims
+        unit = (2 * np.pi / b.alat) ** 2
+        kmax = int(np.floor(2.0 * np.sqrt(2.0 * b.ecut) * b.alat / (2 * np.pi)))
+        axes = [np.arange(-min(kmax, (n - 1) // 2), min(kmax, (n - 1) // 2) + 1) for n in dims]
+        kx, ky, kz = np.meshgrid(*axes, indexing="ij")
+        g2 = unit * (kx ** 2 + ky ** 2 + kz ** 2)
+        m = 0.5 * g2 <= 4.0 * b.ecut + 1e-12
+        trip = np.stack([kx[m], ky[m], kz[m]], axis=1).astype(np.int32)
+        # stick-major order, as PlaneWaveBasis
+        st = [np.where(trip[:, d] < 0, trip[:, d] + dims[d], trip[:, d]).astype(np.int64)
+              for d in range(3)]
+        trip = trip[np.argsort((st[0] * dims[1] + st[1]) * dims[2] + st[2], kind="stable")]
+        g2 = unit * (trip.astype(np.float64) ** 2).sum(axis=1)
+        t0 = self.transforms[0]
+        khost = np.where(g2 > 0, 4.0 * np.pi / np.where(g2 > 0, g2, 1.0), 0.0).astype(t0._prec.real)
+        from ..grid import Grid, GridFloat
+        n0, n1, n2 = dims
+        g = (GridFloat if t0._prec.single else Grid)(n0, n1, n2, n0 * n1, self.pu, -1)
+        t = g.create_transform(self.pu, TransformType.C2C, n0, n1, n2, n2, trip)
+        k = khost
+        if self.pu == ProcessingUnit.GPU:
+            import torch
+            k = torch.as_tensor(khost, device=f"cuda:{t.device_id}")
+        self._exchange = (t, trip, khost, k)
+        return self._exchange
+
+    @property
+    def exchange_transform(self):
+        return self._exchange_setup()[0]
+
+    @property
+    def exchange_indices(self):
+        return self._exchange_setup()[1]
+
+    @property
+    def exchange_kernel_host(self):
+        return self._exchange_setup()[2]
+
+    def exchange_operator(self, psi: Sequence, occupations: Sequence[float],
+                          unfused: bool = False) -> List:
+        """Exact-exchange (Fock) operator of hybrid functionals on every band b, up to the
+        cell-volume prefactor: the coefficients of
+        sum_a -f_a psi_a(r) FFT^-1[ K(G) FFT[conj(psi_a) psi_b](G) ](r)
+        over the occupied bands a (f_a != 0), projected back on the basis.
+
+        The bands go to real space once with the model's transforms; every pair (a, b)
+        is then one accumulate_fock call on the pair-density transform (on the GPU the
+        forward x stage forms conj(a) b in its loads, the backward x stage adds
+        -f_a a u to its rows of the accumulator from LDS, and no pair array goes through
+        memory); `unfused` runs the composition product, apply_reciprocal, addcmul."""
+        t0 = self.transforms[0]
+        tx, _, _, k = self._exchange_setup()
+        psi, occupations = list(psi), [float(f) for f in occupations]
+        real = []
+        for c in psi:
+            s = t0.backward(c)
+            real.append(s.clone() if hasattr(s, "clone") else np.array(s))
+        occupied = [(f, a) for f, a in zip(occupations, real) if f != 0.0]
+        out = []
+        for b in real:
+            acc = b.new_zeros(b.shape) if hasattr(b, "new_zeros") else np.zeros_like(b)
+            for f, a in occupied:
+                if not unfused:
+                    tx.accumulate_fock(a, b, k, -f, acc, scaling=Scaling.FULL)
+                    continue
+                # the product written straight into the space domain
+                space = tx.space_domain(self.pu)
+                if hasattr(acc, "addcmul_"):
+                    import torch
+                    torch.mul(a.conj(), b, out=space)
+                    acc.addcmul_(a, tx.apply_reciprocal(k, scaling=Scaling.FULL), value=-f)
+                else:
+                    np.multiply(np.conj(a), b, out=space)
+                    acc += -f * a * tx.apply_reciprocal(k, scaling=Scaling.FULL)
+            c = t0.forward(space=acc, scaling=Scaling.FULL)
+            out.append(c.clone() if hasattr(c, "clone") else np.array(c))
+        return out
 
     def kinetic(self, psi: Sequence) -> List:
         """T psi_b = |G|^2/2 c_G (diagonal in the plane-wave basis)."""

@@ -130,6 +130,9 @@ def _prototypes(lib):
     for pre in ("spfft_amd_", "spfft_amd_float_"):
         sig[pre + "transform_apply_reciprocal"] = [V, I, D, I, D, I]
         sig[pre + "transform_reciprocal_fused"] = [V, c_int_p]
+    for pre, real in (("spfft_amd_", ctypes.c_double), ("spfft_amd_float_", ctypes.c_float)):
+        sig[pre + "transform_accumulate_fock"] = [V, D, D, D, I, real, D, D, I]
+        sig[pre + "transform_fock_fused"] = [V, c_int_p]
     sig["spfft_amd_timing_enable"] = [I]
     sig["spfft_amd_timing_reset"] = []
     sig["spfft_amd_timing_json"] = [ctypes.c_char_p, ctypes.c_size_t, c_size_t_p]

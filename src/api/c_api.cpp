@@ -631,6 +631,32 @@ SpfftError spfft_amd_float_transform_reciprocal_fused(SpfftFloatTransform t, int
       t, [&](TransformFloat& x) { *fused = x.impl()->reciprocal_fused() ? 1 : 0; });
 }
 
+SpfftError spfft_amd_transform_accumulate_fock(SpfftTransform t, const double* a, const double* b,
+                                               const double* kernel, int kernelIsComplex,
+                                               double weight, double* acc, double* values,
+                                               SpfftScalingType scaling) {
+  return with_handle<Transform>(t, [&](Transform& x) {
+    x.impl()->accumulate_fock(a, b, kernel, kernelIsComplex != 0, weight, acc, values, scaling);
+  });
+}
+SpfftError spfft_amd_float_transform_accumulate_fock(SpfftFloatTransform t, const float* a,
+                                                     const float* b, const float* kernel,
+                                                     int kernelIsComplex, float weight, float* acc,
+                                                     float* values, SpfftScalingType scaling) {
+  return with_handle<TransformFloat>(t, [&](TransformFloat& x) {
+    x.impl()->accumulate_fock(a, b, kernel, kernelIsComplex != 0, weight, acc, values, scaling);
+  });
+}
+SpfftError spfft_amd_transform_fock_fused(SpfftTransform t, int* fused) {
+  if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
+  return with_handle<Transform>(t, [&](Transform& x) { *fused = x.impl()->fock_fused() ? 1 : 0; });
+}
+SpfftError spfft_amd_float_transform_fock_fused(SpfftFloatTransform t, int* fused) {
+  if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
+  return with_handle<TransformFloat>(
+      t, [&](TransformFloat& x) { *fused = x.impl()->fock_fused() ? 1 : 0; });
+}
+
 SpfftError spfft_amd_timing_enable(int enable) {
   timing::set_level(enable);
   return SPFFT_SUCCESS;

@@ -179,6 +179,17 @@ void TransformImpl<T>::apply_reciprocal(SpfftProcessingUnitType location, const 
   if (!kernel && count > 0) throw InvalidParameterError();
   forward_xy(location);
   forward_exchange(false);
+  reciprocal_z(kernel, complexKernel, values, scaling);
+  backward_exchange(false);
+  backward_xy(location);
+  if (gpu_ && gpu_->synchronous()) gpu_->synchronize();
+}
+
+// the stage between the two exchanges of apply_reciprocal and accumulate_fock
+template <typename T>
+void TransformImpl<T>::reciprocal_z(const T* kernel, bool complexKernel, T* values,
+                                    SpfftScalingType scaling) {
+  const std::size_t count = static_cast<std::size_t>(plan_->numLocalElements);
   if (gpu_) {
     gpu_->reciprocal_z(kernel, complexKernel, values, scaling);
   } else {
@@ -201,8 +212,52 @@ void TransformImpl<T>::apply_reciprocal(SpfftProcessingUnitType location, const 
     }
     host_->backward_z(work.data());
   }
+}
+
+template <typename T>
+void TransformImpl<T>::accumulate_fock(const T* a, const T* b, const T* kernel, bool complexKernel,
+                                       T weight, T* acc, T* values, SpfftScalingType scaling) {
+  SPFFT_TIMED_SCOPE("accumulate_fock");
+  if (scaling != SPFFT_NO_SCALING && scaling != SPFFT_FULL_SCALING) throw InvalidParameterError();
+  const IndexPlan& p = *plan_;
+  const std::size_t space = static_cast<std::size_t>(p.local_planes()) * p.dimY * p.dimX;
+  if (space > 0 && (!a || !b || !acc)) throw InvalidParameterError();
+  if (!kernel && p.numLocalElements > 0) throw InvalidParameterError();
+  const bool real = p.type == SPFFT_TRANS_R2C;
+  if (gpu_) {
+    gpu_->fock_forward_xy(a, b);
+  } else {
+    // host: the plain composition through the space domain
+    T* s = host_->space_domain();
+    if (real) {
+      for (std::size_t i = 0; i < space; ++i) s[i] = a[i] * b[i];
+    } else {
+      for (std::size_t i = 0; i < space; ++i) {
+        const T ar = a[2 * i], ai = a[2 * i + 1], br = b[2 * i], bi = b[2 * i + 1];
+        s[2 * i] = ar * br + ai * bi;
+        s[2 * i + 1] = ar * bi - ai * br;
+      }
+    }
+    host_->forward_xy();
+  }
+  forward_exchange(false);
+  reciprocal_z(kernel, complexKernel, values, scaling);
   backward_exchange(false);
-  backward_xy(location);
+  if (gpu_) {
+    gpu_->fock_backward_xy(a, acc, weight);
+  } else {
+    host_->backward_xy();
+    const T* u = host_->space_domain();
+    if (real) {
+      for (std::size_t i = 0; i < space; ++i) acc[i] += weight * a[i] * u[i];
+    } else {
+      for (std::size_t i = 0; i < space; ++i) {
+        const T tr = weight * a[2 * i], ti = weight * a[2 * i + 1];
+        acc[2 * i] += tr * u[2 * i] - ti * u[2 * i + 1];
+        acc[2 * i + 1] += tr * u[2 * i + 1] + ti * u[2 * i];
+      }
+    }
+  }
   if (gpu_ && gpu_->synchronous()) gpu_->synchronize();
 }
 

@@ -51,6 +51,16 @@ public:
                         T* values, SpfftScalingType scaling);
   bool reciprocal_fused() const { return gpu_ && gpu_->reciprocal_fused(); }
 
+  // Exchange (Fock) pair operator: acc += weight * a * backward(K * (scale *
+  // forward(conj(a) * b))) with a, b and acc over the local space domain
+  // [localZ][dimY][dimX] (interleaved complex; real for R2C, where conj is the
+  // identity). kernel and values as in apply_reciprocal. a and b are not
+  // modified (a == b is allowed); the space domain's contents are unspecified
+  // afterwards (untouched on the fused GPU path).
+  void accumulate_fock(const T* a, const T* b, const T* kernel, bool complexKernel, T weight, T* acc,
+                       T* values, SpfftScalingType scaling);
+  bool fock_fused() const { return gpu_ && gpu_->fock_fused(); }
+
   void forward_xy(SpfftProcessingUnitType inputLocation);
   void forward_exchange(bool nonBlocking);
   void forward_z(T* output, SpfftScalingType scaling);
@@ -71,6 +81,7 @@ public:
 
 private:
   void create_executor();
+  void reciprocal_z(const T* kernel, bool complexKernel, T* values, SpfftScalingType scaling);
 
   std::shared_ptr<GridImpl<T>> grid_;
   SpfftProcessingUnitType exec_;

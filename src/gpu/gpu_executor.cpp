@@ -70,6 +70,9 @@ GpuExecutor<T>::GpuExecutor(std::shared_ptr<GridImpl<T>> grid,
   applyFused_ = p.type == SPFFT_TRANS_C2C && !longX_;
   // accumulate_density runs the fused x density stage under the same conditions
   densityFused_ = applyFused_;
+  // accumulate_fock runs the fused pair x stages under the same conditions (its
+  // z stage follows reciprocalFused_ independently)
+  fockFused_ = applyFused_;
   // apply_reciprocal runs the fused z stage for simple sticks whose z lines fit
   // one workgroup, on a stick side that is not a *_FLOAT exchange buffer and that
   // peers do not write (peerWrites_ is known only further down: see below)
@@ -229,7 +232,7 @@ void GpuExecutor<T>::log_plan() const {
   if (p.size > 1) plane = const_cast<GridImpl<T>&>(*grid_).device_comm().describe();
   std::fprintf(stderr,
                "spfft[gpu rank %d/%d] %dx%dx%d %s %s: sticks=%d planes=%d columns=%d | z{%s} "
-               "y{%s} x{%s}%s inter_planes=%d apply_local=%s density=%s reciprocal=%s | exchange=%s%s plane=%s chunks=%d stick_blocks=%d "
+               "y{%s} x{%s}%s inter_planes=%d apply_local=%s density=%s reciprocal=%s fock=%s | exchange=%s%s plane=%s chunks=%d stick_blocks=%d "
                "steps=%zu+%zu (%.2f MB per peer) peer_writes=%d peer_offsets=[%lld, %lld] "
                "library_streams=%d\n",
                p.rank, p.size, p.dimX, p.dimY, p.dimZ,
@@ -239,7 +242,7 @@ void GpuExecutor<T>::log_plan() const {
                describe(longX_, lpX_, twXh_ ? p.dimX / 2 : p.dimX, true).c_str(),
                twXh_ ? " packed-real" : "", interPlanes_, applyFused_ ? "fused" : "unfused",
                densityFused_ ? "fused" : "composed", reciprocalFused_ ? "fused" : "composed",
-               layout_.buffered ? "buffered" : "compact",
+               fockFused_ ? "fused" : "composed", layout_.buffered ? "buffered" : "compact",
                floatExchange_ ? "-float" : "", plane.c_str(), exchChunks_, stickBlocks_, bwdSteps_.size(),
                fwdSteps_.size(), chunkModel_ / 1e6, peerWrites_ ? 1 : 0, peerOffsetRange_[0],
                peerOffsetRange_[1], GpuStream::live());
@@ -1141,15 +1144,10 @@ cx<T>* GpuExecutor<T>::inter_for(cx<T>* inter, int z0) const {
 }
 
 template <typename T>
-void GpuExecutor<T>::backward_xy(SpfftProcessingUnitType outputLocation) {
-  SPFFT_TIMED_SCOPE("gpu_backward_xy");
-  if (outputLocation != SPFFT_PU_HOST && outputLocation != SPFFT_PU_GPU)
-    throw InvalidParameterError();
-  DeviceGuard guard(deviceId_);
-  StageEnd stageEnd{this, "backward", pipelined() ? "exchange+y+x" : "y+x"};
+template <class XLaunch>
+void GpuExecutor<T>::backward_yx_ranges(XLaunch xLaunch) {
   void* slab = grid_->device_slot(GridImpl<T>::kSlabSide);
   auto* inter = static_cast<cx<T>*>(grid_->device_slot(GridImpl<T>::kInter));
-  void* space = grid_->device_slot(GridImpl<T>::kSpace);
   if (peerWrites_) grid_->device_comm().note_read(GridImpl<T>::kSlabSide);
   // pipelined exchange: the y/x stages of chunk k start when it has arrived;
   // within a chunk, plane ranges of at most interPlanes_ reuse the intermediate
@@ -1171,9 +1169,20 @@ void GpuExecutor<T>::backward_xy(SpfftProcessingUnitType outputLocation) {
       ya.plainSticks = plainHandoff_;
       cx<T>* in = inter_for(inter, z0);
       y_backward_launch(ya, slab, in);
-      x_backward_launch(xa, in, space);
+      xLaunch(xa, in);
     }
   }
+}
+
+template <typename T>
+void GpuExecutor<T>::backward_xy(SpfftProcessingUnitType outputLocation) {
+  SPFFT_TIMED_SCOPE("gpu_backward_xy");
+  if (outputLocation != SPFFT_PU_HOST && outputLocation != SPFFT_PU_GPU)
+    throw InvalidParameterError();
+  DeviceGuard guard(deviceId_);
+  StageEnd stageEnd{this, "backward", pipelined() ? "exchange+y+x" : "y+x"};
+  void* space = grid_->device_slot(GridImpl<T>::kSpace);
+  backward_yx_ranges([&](const dev::XArgs& xa, cx<T>* in) { x_backward_launch(xa, in, space); });
   if (outputLocation == SPFFT_PU_HOST) {
     gpu_check(hipMemcpyAsync(grid_->host_slot(GridImpl<T>::kSpace), space, space_bytes(),
                              hipMemcpyDeviceToHost, stream_),
@@ -1198,6 +1207,12 @@ void GpuExecutor<T>::forward_xy(SpfftProcessingUnitType inputLocation) {
               "hipMemcpyAsync");
   }
   poison(false);
+  forward_xy_ranges([&](const dev::XArgs& xa, cx<T>* out) { x_forward_launch(xa, space, out); });
+}
+
+template <typename T>
+template <class XLaunch>
+void GpuExecutor<T>::forward_xy_ranges(XLaunch xLaunch) {
   auto* inter = static_cast<cx<T>*>(grid_->device_slot(GridImpl<T>::kInter));
   void* slab = grid_->device_slot(GridImpl<T>::kSlabSide);
   // the y stage stores straight into the peers' stick sides
@@ -1222,7 +1237,7 @@ void GpuExecutor<T>::forward_xy(SpfftProcessingUnitType inputLocation) {
         set_col_desc(ya, colDescRemote_);
       }
       cx<T>* out = inter_for(inter, z0);
-      x_forward_launch(xa, space, out);
+      xLaunch(xa, out);
       y_forward_launch(ya, out, slab);
     }
     if (pipe) chunkEv_[k]->record(stream_);
@@ -1486,35 +1501,95 @@ void GpuExecutor<T>::accumulate_density_xy(T* density, T weight, GpuExecutor* af
   } else {
     const bool pipe = pipelined();
     StageEnd stageEnd{this, "backward", pipe ? "exchange+y+x_density" : "y+x_density"};
-    void* slab = grid_->device_slot(GridImpl<T>::kSlabSide);
-    auto* inter = static_cast<cx<T>*>(grid_->device_slot(GridImpl<T>::kInter));
-    if (peerWrites_) grid_->device_comm().note_read(GridImpl<T>::kSlabSide);
-    const int K = pipe ? exchChunks_ : 1;
-    for (int k = 0; k < K; ++k) {
-      if (pipe) chunkEv_[k]->wait_on(stream_);  // chunk k has arrived
-      const int zb = pipe ? planeBounds_[k] : 0;
-      const int ze = pipe ? planeBounds_[k + 1] : p.local_planes();
-      for (int z0 = zb; z0 < ze; z0 += interPlanes_) {
-        auto ya = yargs();
-        auto xa = xargs();
-        ya.zBegin = xa.zBegin = z0;
-        ya.L = xa.L = std::min(ze, z0 + interPlanes_);
-        if (pipe) {
-          ya.colBase = colBaseChunk_[k] ? colBaseChunk_[k]->data<long long>() : nullptr;
-          set_col_desc(ya, colDescChunk_[k]);
-        }
-        ya.plainSticks = plainHandoff_;
-        cx<T>* tile = inter_for(inter, z0);
-        y_backward_launch(ya, slab, tile);
-        order_after_density(after);  // (once: the stream stays behind it)
-        after = nullptr;
-        dev::launch_x_density<T>(xa, tile, rho, &weight, twX_->data<cx<T>>(), stream_);
-      }
-    }
+    backward_yx_ranges([&](const dev::XArgs& xa, cx<T>* tile) {
+      order_after_density(after);  // (once: the stream stays behind it)
+      after = nullptr;
+      dev::launch_x_density<T>(xa, tile, rho, &weight, twX_->data<cx<T>>(), stream_);
+    });
   }
   if (staged)
     gpu_check(hipMemcpyAsync(density, rho, count * sizeof(T), hipMemcpyDeviceToHost, stream_),
               "hipMemcpyAsync");
+}
+
+// ------------------------------------------------- exchange (Fock) pair operator
+// accumulate_fock = fock_forward_xy, forward_exchange, reciprocal_z,
+// backward_exchange, fock_backward_xy (TransformImpl::accumulate_fock). Fused
+// plans (C2C, x lines of one workgroup) run the loops of forward_xy and
+// backward_xy with the pair x stages and never form the space domain; other
+// plans pass through it with one pointwise kernel at either end. Host a, b and
+// acc are staged through device buffers on the stream.
+template <typename T>
+std::size_t GpuExecutor<T>::space_elements() const {
+  const IndexPlan& p = *plan_;
+  return static_cast<std::size_t>(p.local_planes()) * p.dimY * p.dimX;
+}
+
+template <typename T>
+void GpuExecutor<T>::fock_forward_xy(const T* a, const T* b) {
+  SPFFT_TIMED_SCOPE("gpu_fock_forward_xy");
+  DeviceGuard guard(deviceId_);
+  const IndexPlan& p = *plan_;
+  const std::size_t count = space_elements();
+  if (count > 0 && (!a || !b)) throw InvalidParameterError();
+  const bool real = p.type == SPFFT_TRANS_R2C;
+  const std::size_t bytes = count * (real ? sizeof(T) : sizeof(cx<T>));
+  order_after_default_stream();
+  stage_mark("forward", nullptr);
+  auto device = [&](const T* src, std::unique_ptr<DeviceBuffer>& buf) -> const T* {
+    if (count == 0 || is_device_pointer(src)) return src;
+    if (!buf || buf->bytes() < bytes) buf.reset(new DeviceBuffer(bytes));
+    gpu_check(hipMemcpyAsync(buf->data<T>(), src, bytes, hipMemcpyHostToDevice, stream_), "hipMemcpyAsync");
+    return buf->data<T>();
+  };
+  const T* da = device(a, fockA_);
+  const T* db = b == a ? da : device(b, fockB_);
+  if (!fockFused_) {
+    dev::launch_space_pair<T>(grid_->device_slot(GridImpl<T>::kSpace), da, db, static_cast<long long>(count),
+                              real, stream_);
+    stage_mark("forward", "pair");
+    forward_xy(SPFFT_PU_GPU);
+    return;
+  }
+  StageEnd stageEnd{this, "forward", "x_pair+y"};
+  poison(false);
+  forward_xy_ranges([&](const dev::XArgs& xa, cx<T>* out) {
+    dev::launch_x_forward_pair<T>(xa, reinterpret_cast<const cx<T>*>(da), reinterpret_cast<const cx<T>*>(db), out,
+                                  twX_->data<cx<T>>(), stream_);
+  });
+}
+
+template <typename T>
+void GpuExecutor<T>::fock_backward_xy(const T* a, T* acc, T weight) {
+  SPFFT_TIMED_SCOPE("gpu_fock_backward_xy");
+  DeviceGuard guard(deviceId_);
+  const IndexPlan& p = *plan_;
+  const std::size_t count = space_elements();
+  if (count > 0 && (!a || !acc)) throw InvalidParameterError();
+  const bool real = p.type == SPFFT_TRANS_R2C;
+  const std::size_t bytes = count * (real ? sizeof(T) : sizeof(cx<T>));
+  // a host `a` is still in the buffer fock_forward_xy staged it in
+  const T* da = count == 0 || is_device_pointer(a) ? a : fockA_->data<T>();
+  T* dacc = acc;
+  const bool staged = count > 0 && !is_device_pointer(acc);
+  if (staged) {
+    if (!fockAcc_ || fockAcc_->bytes() < bytes) fockAcc_.reset(new DeviceBuffer(bytes));
+    dacc = fockAcc_->data<T>();
+    gpu_check(hipMemcpyAsync(dacc, acc, bytes, hipMemcpyHostToDevice, stream_), "hipMemcpyAsync");
+  }
+  if (!fockFused_) {
+    backward_xy(SPFFT_PU_GPU);
+    dev::launch_space_fock<T>(grid_->device_slot(GridImpl<T>::kSpace), da, dacc, weight,
+                              static_cast<long long>(count), real, stream_);
+    stage_mark("backward", "fock");
+  } else {
+    StageEnd stageEnd{this, "backward", pipelined() ? "exchange+y+x_fock" : "y+x_fock"};
+    backward_yx_ranges([&](const dev::XArgs& xa, cx<T>* tile) {
+      dev::launch_x_backward_fock<T>(xa, tile, reinterpret_cast<const cx<T>*>(da), reinterpret_cast<cx<T>*>(dacc),
+                                     weight, twX_->data<cx<T>>(), stream_);
+    });
+  }
+  if (staged) gpu_check(hipMemcpyAsync(acc, dacc, bytes, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync");
 }
 
 // ------------------------------------------------------- batched multi-transform

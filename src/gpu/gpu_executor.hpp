@@ -105,6 +105,20 @@ public:
   void reciprocal_z(const T* kernel, bool complexKernel, T* values, SpfftScalingType scaling);
   bool reciprocal_fused() const { return reciprocalFused_; }
 
+  // Exchange (Fock) pair operator (TransformImpl::accumulate_fock): the stages
+  // in front of forward_exchange and behind backward_exchange; reciprocal_z
+  // runs between the two exchanges. a, b and acc cover the local space domain
+  // [localZ][dimY][dimX] (interleaved complex, or real for R2C) and are host or
+  // device pointers (host arrays are staged on the stream). Fused plans (C2C, x
+  // lines of one workgroup) run the loops of forward_xy / backward_xy with the
+  // pair x stages (rows conj(a) * b into the forward x FFT; acc += weight * a *
+  // inverse x FFT from LDS) and leave the space domain untouched; other plans
+  // run space = conj(a) * b, forward_xy and backward_xy, acc += weight * a *
+  // space. fock_backward_xy takes the `a` given to fock_forward_xy.
+  void fock_forward_xy(const T* a, const T* b);
+  void fock_backward_xy(const T* a, T* acc, T weight);
+  bool fock_fused() const { return fockFused_; }
+
   void synchronize();
   bool synchronous() const { return synchronous_; }
   // Execute on `stream` (nullptr = the legacy default stream); work is then
@@ -146,6 +160,9 @@ private:
   std::unique_ptr<GpuEvent> densityEvent_;
   bool reciprocalFused_ = false;
   std::unique_ptr<DeviceBuffer> recKernel_;  // stages a host kernel
+  bool fockFused_ = false;
+  std::unique_ptr<DeviceBuffer> fockA_, fockB_, fockAcc_;  // stage host a, b, acc
+  std::size_t space_elements() const;  // elements of the local space domain
   struct GraphEntry {
     int dir;  // 0 backward, 1 forward
     const void* in;
@@ -176,6 +193,14 @@ private:
   void x_backward_launch(const dev::XArgs& xa, const cx<T>* inter, void* space);
   void x_forward_launch(const dev::XArgs& xa, const void* space, cx<T>* inter);
   cx<T>* inter_for(cx<T>* inter, int z0) const;
+  // The launch loops of the y/x stages over exchange chunks and plane ranges of
+  // the intermediate, with the events and the peer-write bookkeeping of the
+  // pipelined and peer-written exchanges. xLaunch(xa, inter) enqueues the x
+  // stage of one plane range: backward behind its y stage, forward in front.
+  template <class XLaunch>
+  void backward_yx_ranges(XLaunch xLaunch);
+  template <class XLaunch>
+  void forward_xy_ranges(XLaunch xLaunch);
   bool poison_ = false;        // SPFFT_POISON=1: NaN-fill work buffers before each direction
   int deviceId_ = 0;
 

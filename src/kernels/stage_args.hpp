@@ -177,6 +177,25 @@ template <typename T>
 void launch_space_density(const void* space, T* density, T weight, long long count, bool realSpace,
                           hipStream_t stream);
 
+// Exchange (Fock) pair operator, fused x stages of C2C transforms. Forward: the
+// x stage of forward_xy whose rows are conj(a) * b of two space-domain arrays
+// [z][y][x]. Backward: the x stage of backward_xy whose result u is not stored:
+// acc[z][y][x] += weight * a[z][y][x] * u[z][y][x].
+template <typename T>
+void launch_x_forward_pair(const XArgs& a, const cx<T>* pa, const cx<T>* pb, cx<T>* inter, const cx<T>* tw,
+                           hipStream_t stream);
+template <typename T>
+void launch_x_backward_fock(const XArgs& a, const cx<T>* inter, const cx<T>* pa, cx<T>* acc, T weight,
+                            const cx<T>* tw, hipStream_t stream);
+// Composed path, one pass each: space[i] = conj(a[i]) * b[i] and acc[i] +=
+// weight * a[i] * space[i] (interleaved complex or, realSpace, real arrays).
+template <typename T>
+void launch_space_pair(void* space, const T* pa, const T* pb, long long count, bool realSpace,
+                       hipStream_t stream);
+template <typename T>
+void launch_space_fock(const void* space, const T* pa, T* acc, T weight, long long count, bool realSpace,
+                       hipStream_t stream);
+
 // Largest run-time FFT length supported in one workgroup (LDS-resident).
 int max_device_fft_length(bool doublePrecision);
 // true if n has a compile-time (register-resident) kernel: the powers of two

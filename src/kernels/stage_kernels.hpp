@@ -462,8 +462,28 @@ __device__ __forceinline__ cx<T> row_elem(const E* p) {
   else
     return ld_stream(p);
 }
-template <class Eng, typename T, typename E>
-__device__ __forceinline__ void stage_rows(const Eng& eng, cx<T>* lds, int rows, int len, RowSrc<E> src) {
+// Pair row source (x_forward_pair_kernel): the element staged is conj(a) * b of
+// two arrays with one row layout. PairPtr stands in for RowSrc's element
+// pointer; Stream: the cache policy of both loads (non-temporal or plain).
+template <typename T, bool Stream>
+struct PairPtr {
+  const cx<T>* a;
+  const cx<T>* b;
+  __device__ __forceinline__ PairPtr operator+(long long d) const { return PairPtr{a + d, b + d}; }
+};
+template <typename T, bool Stream>
+struct PairSrc {
+  PairPtr<T, Stream> base;
+  long long stride;
+};
+template <typename T, bool Stream>
+__device__ __forceinline__ cx<T> row_elem(PairPtr<T, Stream> p) {
+  if constexpr (Stream) return cmulc(ld_stream(p.b), ld_stream(p.a));
+  else return cmulc(*p.b, *p.a);
+}
+// Src: RowSrc<E> or PairSrc<T, Stream>
+template <class Eng, typename T, class Src>
+__device__ __forceinline__ void stage_rows(const Eng& eng, cx<T>* lds, int rows, int len, Src src) {
   if constexpr (!Eng::kBatchedCopy) {
     // full tile of a compile-time engine: the trip count, and each unrolled
     // load's row and position offsets, are compile-time (the row products are
@@ -482,14 +502,14 @@ __device__ __forceinline__ void stage_rows(const Eng& eng, cx<T>* lds, int rows,
         if constexpr (NT % N == 0) {
           constexpr int RP = NT / N;  // rows per pass of the workgroup
           const int b0 = tid / N, p = tid % N;
-          const E* p0 = src.base + static_cast<long long>(b0) * src.stride + p;
+          const auto p0 = src.base + static_cast<long long>(b0) * src.stride + p;
 #pragma unroll
           for (int i = 0; i < kIters; ++i) v[i] = row_elem<T>(p0 + (i * RP) * src.stride);
 #pragma unroll
           for (int i = 0; i < kIters; ++i) lds[eng.in_at(b0 + i * RP, p)] = v[i];
         } else {
           constexpr int C = N / NT;  // passes per row
-          const E* p0 = src.base + tid;
+          const auto p0 = src.base + tid;
 #pragma unroll
           for (int i = 0; i < kIters; ++i) v[i] = row_elem<T>(p0 + (i / C) * src.stride + (i % C) * NT);
 #pragma unroll
@@ -1686,6 +1706,149 @@ __global__ void __launch_bounds__(256)
       s2 = norm2(ld_stream(space + i));
     }
     st_stream_real(density + i, fma(w, s2, ld_stream_real(density + i)));
+  }
+}
+
+// ------------------------------------------------ exchange (Fock) pair operator
+// accumulate_fock: acc += w a backward(K forward(conj(a) b)). Fused plans (C2C)
+// form the pair density in the forward x stage's row loads and accumulate in
+// the backward x stage's copy-out; the space domain is neither written nor read.
+
+// Forward x stage of the pair density: x_forward_kernel (C2C) whose tile rows
+// are conj(a) * b of two space-domain arrays. StreamAB: the cache policy of
+// their loads (a template parameter: a run-time flag costs registers and can
+// lose the hint, profiles/r6/ntmerge). a may be b: both are only read.
+template <class Eng, typename T, bool StreamAB>
+__global__ void __launch_bounds__(Eng::kBlock)
+    x_forward_pair_kernel(Eng eng, XArgs a, const cx<T>* __restrict__ pa, const cx<T>* __restrict__ pb,
+                          cx<T>* __restrict__ inter, const cx<T>* __restrict__ tw) {
+  SPFFT_LDS_DECL(T);
+  const int B = eng.lines();
+  const int n = eng.n();
+  int tx, ty;
+  block_tile(tx, ty);
+  const int zl = a.zBegin + ty;
+  const int y0 = tx * B;
+  int* xCol = reinterpret_cast<int*>(reinterpret_cast<char*>(lds) + eng.lds_bytes());
+  build_xcol(a, xCol, n);
+  const int yl = min(B, a.Y - y0);
+  cx<T>* dst = inter + static_cast<long long>(zl) * a.interZStride + y0;
+  const long long row0 = (static_cast<long long>(zl) * a.Y + y0) * n;
+  // arguments of the per-element stores pinned in scalar registers (see x_backward_kernel)
+  const int rowStride = pin_uniform(static_cast<int>(a.interStride)), nFreq = pin_uniform(a.nFreq);
+  const int dense = pin_uniform(x_dense(a) ? 1 : 0);
+  auto store = [&](int b, int pos, cx<T> v) {
+    const int c = dense ? (pos < nFreq ? pos : -1) : xCol[pos];
+    if (c >= 0 && b < yl) st_inter(&dst[c * rowStride + b], v);
+  };
+  stage_rows(eng, lds, yl, n, PairSrc<T, StreamAB>{{pa + row0, pb + row0}, n});
+  eng.lds_to_global(lds, tw, store);
+}
+
+// acc[idx] += w a[idx] lds[src(idx)] for idx in [0, total): lanes walk the rows
+// contiguously (the order of copy_out). kFockUnroll loads each of a and acc are
+// in flight per lane before the first dependent store (acc is not restrict
+// against itself: the compiler may not move a load of acc over a store to it).
+// The unroll is small for the reason given at density_rows: two complex values
+// per element are live on top of the engine's registers.
+constexpr int kFockUnroll = 4;
+template <bool Stream, typename T, class Src>
+__device__ __forceinline__ void fock_rows(const cx<T>* lds, const cx<T>* __restrict__ pa, cx<T>* __restrict__ acc,
+                                          T w, int total, Src src) {
+  for (int base = threadIdx.x; base < total; base += blockDim.x * kFockUnroll) {
+    cx<T> av[kFockUnroll], r[kFockUnroll];
+#pragma unroll
+    for (int u = 0; u < kFockUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        if constexpr (Stream) {
+          av[u] = ld_stream(pa + idx);
+          r[u] = ld_stream(acc + idx);
+        } else {
+          av[u] = pa[idx];
+          r[u] = acc[idx];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kFockUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        const cx<T> t = scale(av[u], w);
+        const cx<T> v = lds[src(idx)];
+        const cx<T> o = mk<T>(fma(t.x, v.x, fma(-t.y, v.y, r[u].x)), fma(t.x, v.y, fma(t.y, v.x, r[u].y)));
+        if constexpr (Stream) st_stream(acc + idx, o);
+        else acc[idx] = o;
+      }
+    }
+  }
+}
+
+// Backward x stage of the pair operator: the front half of x_backward_kernel
+// (C2C: same tile, column lookup and engine), then acc += w a u on the
+// workgroup's rows of acc straight from LDS. A workgroup owns its tile's rows of
+// acc, so the update needs no atomics. StreamAcc: cache policy of a and acc.
+template <class Eng, typename T, bool StreamAcc>
+__global__ void __launch_bounds__(Eng::kBlock)
+    x_backward_fock_kernel(Eng eng, XArgs a, const cx<T>* __restrict__ inter, const cx<T>* __restrict__ pa,
+                           cx<T>* __restrict__ acc, T w, const cx<T>* __restrict__ tw) {
+  SPFFT_LDS_DECL(T);
+  const int B = eng.lines();
+  const int n = eng.n();
+  int tx, ty;
+  block_tile(tx, ty);
+  const int zl = a.zBegin + ty;
+  const int y0 = tx * B;
+  int* xCol = reinterpret_cast<int*>(reinterpret_cast<char*>(lds) + eng.lds_bytes());
+  build_xcol(a, xCol, n);
+  const cx<T>* src = inter + static_cast<long long>(zl) * a.interZStride + y0;
+  const int yl = min(B, a.Y - y0);
+  // per-element arguments pinned in scalar registers (see x_backward_kernel)
+  const int rowStride = pin_uniform(static_cast<int>(a.interStride)), nFreq = pin_uniform(a.nFreq);
+  const int dense = pin_uniform(x_dense(a) ? 1 : 0);
+  auto col_of = [&](int x) { return dense ? (x < nFreq ? x : -1) : xCol[x]; };
+  auto load = [&](int b, int pos) -> cx<T> {
+    if (b >= yl) return czero<T>();
+    const int c = col_of(pos);
+    return c < 0 ? czero<T>() : ld_inter(&src[c * rowStride + b]);
+  };
+  const long long row0 = (static_cast<long long>(zl) * a.Y + y0) * n;
+  eng.global_to_lds(lds, tw, load);  // rows at out_at(b, x); ends with a barrier
+  fock_rows<StreamAcc>(lds, pa + row0, acc + row0, w, yl * n, [&](int idx) {
+    const int b = idx / n;
+    return eng.out_at(b, idx - b * n);
+  });
+}
+
+// The composed pair operator's two passes over the space domain (R2C transforms
+// and long x lines): E = cx<T> or T (conj is then the identity).
+// space[i] = conj(a[i]) * b[i]
+template <typename E, typename T>
+__global__ void __launch_bounds__(256)
+    space_pair_kernel(E* __restrict__ space, const E* pa, const E* pb, long long count) {
+  const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
+  for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride) {
+    if constexpr (std::is_same<E, T>::value)
+      st_stream_real(space + i, ld_stream_real(pa + i) * ld_stream_real(pb + i));
+    else
+      st_stream(space + i, cmulc(ld_stream(pb + i), ld_stream(pa + i)));
+  }
+}
+// acc[i] += w * a[i] * space[i]
+template <typename E, typename T>
+__global__ void __launch_bounds__(256)
+    space_fock_kernel(const E* __restrict__ space, const E* __restrict__ pa, E* __restrict__ acc, T w,
+                      long long count) {
+  const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
+  for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride) {
+    if constexpr (std::is_same<E, T>::value) {
+      st_stream_real(acc + i, fma(w * ld_stream_real(pa + i), ld_stream_real(space + i), ld_stream_real(acc + i)));
+    } else {
+      const cx<T> t = scale(ld_stream(pa + i), w);
+      const cx<T> v = ld_stream(space + i);
+      const cx<T> r = ld_stream(acc + i);
+      st_stream(acc + i, mk<T>(fma(t.x, v.x, fma(-t.y, v.y, r.x)), fma(t.x, v.y, fma(t.y, v.x, r.y))));
+    }
   }
 }
 

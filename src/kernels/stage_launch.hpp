@@ -257,5 +257,75 @@ void launch_space_density(const void* space, T* density, T weight, long long cou
   gpu_check_launch("space_density", stream);
 }
 
+// Cache policy of the fused pair operator's space-array accesses (a, b in the
+// forward x stage; a, acc in the backward x stage): streaming (1) or plain (0).
+#ifndef SPFFT_FOCK_STREAM
+#define SPFFT_FOCK_STREAM 1
+#endif
+
+// Forward x stage of the pair density (C2C): rows conj(a) * b, launch geometry
+// of launch_x_forward.
+template <typename T>
+void launch_x_forward_pair(const XArgs& a, const cx<T>* pa, const cx<T>* pb, cx<T>* inter, const cx<T>* tw,
+                           hipStream_t stream) {
+  if (a.L <= a.zBegin || a.Y <= 0) return;
+  with_engine<T, -1, true>(a.n, [&](auto eng, int threads, int lines, std::size_t lds) {
+    auto k = x_forward_pair_kernel<decltype(eng), T, SPFFT_FOCK_STREAM != 0>;
+    const std::size_t ldsTotal = lds + std::size_t(a.n) * sizeof(int) + 16;
+    prepare_kernel(k, ldsTotal);
+    hipLaunchKernelGGL(k, dim3(ceil_div(a.Y, lines), a.L - a.zBegin, 1), dim3(threads), ldsTotal, stream, eng, a,
+                       pa, pb, inter, tw);
+    gpu_check_launch("x_forward_pair", stream);
+  });
+}
+
+// Backward x stage of the pair operator (C2C): acc += weight * a * inverse x
+// FFT, launch geometry of launch_x_backward.
+template <typename T>
+void launch_x_backward_fock(const XArgs& a, const cx<T>* inter, const cx<T>* pa, cx<T>* acc, T weight,
+                            const cx<T>* tw, hipStream_t stream) {
+  if (a.L <= a.zBegin || a.Y <= 0) return;
+  with_engine<T, +1, true>(a.n, [&](auto eng, int threads, int lines, std::size_t lds) {
+    auto k = x_backward_fock_kernel<decltype(eng), T, SPFFT_FOCK_STREAM != 0>;
+    const std::size_t ldsTotal = lds + std::size_t(a.n) * sizeof(int) + 16;
+    prepare_kernel(k, ldsTotal);
+    hipLaunchKernelGGL(k, dim3(ceil_div(a.Y, lines), a.L - a.zBegin, 1), dim3(threads), ldsTotal, stream, eng, a,
+                       inter, pa, acc, weight, tw);
+    gpu_check_launch("x_backward_fock", stream);
+  });
+}
+
+// space[i] = conj(a[i]) * b[i] over `count` elements (complex or, realSpace, real)
+template <typename T>
+void launch_space_pair(void* space, const T* pa, const T* pb, long long count, bool realSpace,
+                       hipStream_t stream) {
+  if (count <= 0) return;
+  const unsigned blocks = static_cast<unsigned>(std::min<long long>((count + 255) / 256, 256 * 64));
+  if (realSpace)
+    hipLaunchKernelGGL((space_pair_kernel<T, T>), dim3(blocks), dim3(256), 0, stream, static_cast<T*>(space), pa,
+                       pb, count);
+  else
+    hipLaunchKernelGGL((space_pair_kernel<cx<T>, T>), dim3(blocks), dim3(256), 0, stream,
+                       static_cast<cx<T>*>(space), reinterpret_cast<const cx<T>*>(pa),
+                       reinterpret_cast<const cx<T>*>(pb), count);
+  gpu_check_launch("space_pair", stream);
+}
+
+// acc[i] += weight * a[i] * space[i] over `count` elements (complex or, realSpace, real)
+template <typename T>
+void launch_space_fock(const void* space, const T* pa, T* acc, T weight, long long count, bool realSpace,
+                       hipStream_t stream) {
+  if (count <= 0) return;
+  const unsigned blocks = static_cast<unsigned>(std::min<long long>((count + 255) / 256, 256 * 64));
+  if (realSpace)
+    hipLaunchKernelGGL((space_fock_kernel<T, T>), dim3(blocks), dim3(256), 0, stream,
+                       static_cast<const T*>(space), pa, acc, weight, count);
+  else
+    hipLaunchKernelGGL((space_fock_kernel<cx<T>, T>), dim3(blocks), dim3(256), 0, stream,
+                       static_cast<const cx<T>*>(space), reinterpret_cast<const cx<T>*>(pa),
+                       reinterpret_cast<cx<T>*>(acc), weight, count);
+  gpu_check_launch("space_fock", stream);
+}
+
 }  // namespace dev
 }  // namespace spfft

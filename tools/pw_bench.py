@@ -11,7 +11,10 @@ composition of backward and torch passes; --op hartree times
 PlaneWaveModel.hartree_potential, one apply_reciprocal per call, against its
 composition forward, K(G) multiply, backward in alternating rounds of one
 process, and prints the GPU stage times of both and the modelled bytes of the two
-z stages; with --r2c on an R2C transform.)
+z stages; with --r2c on an R2C transform; --op fock times one exchange pair,
+accumulate_fock on the model's pair-density transform (the sphere |G|^2/2 <= 4
+ecut) against torch product, apply_reciprocal, torch addcmul_, with the same
+protocol and the modelled bytes of both.)
 """
 import argparse
 import json
@@ -30,7 +33,7 @@ def main():
     ap.add_argument("--transforms", type=int, default=8)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--unfused", action="store_true")
-    ap.add_argument("--op", choices=("local", "density", "hartree"), default="local")
+    ap.add_argument("--op", choices=("local", "density", "hartree", "fock"), default="local")
     ap.add_argument("--grid", type=int, default=0,
                     help="FFT grid N^3 instead of the density grid of the cutoff (the cutoff "
                          "sphere may then reach N/2, the transforms' own minimum grid)")
@@ -44,6 +47,9 @@ def main():
     basis = PlaneWaveBasis(alat=a.alat, ecut=a.ecut,
                            fft_dims=(a.grid,) * 3 if a.grid else None)
     model = PlaneWaveModel(basis, processing_unit=sp.ProcessingUnit.GPU, num_transforms=a.transforms)
+    if a.op == "fock":
+        fock(a, basis, model)
+        return
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev)
     g.manual_seed(5)
@@ -170,6 +176,79 @@ def hartree(a, basis, model, rho):
                       "gpu_stage_median_s": stages,
                       "model_z_bytes": {"composed": 2 * stick_bytes + 4 * value_bytes + value_bytes // 2,
                                         "fused": 2 * stick_bytes + value_bytes // 2}}), flush=True)
+
+
+def fock(a, basis, model):
+    """One exchange pair (a, b) on the model's pair-density transform: accumulate_fock
+    against its composition (torch product into the space domain, apply_reciprocal, torch
+    addcmul_) in alternating rounds of one process (medians over the rounds), then the
+    GPU stage times of each variant from the timing tree, and the modelled bytes."""
+    import torch
+
+    import spfft_amd as sp
+    nx, ny, nz = basis.fft_dims
+    t = model.exchange_transform
+    idx = model.exchange_indices
+    k = model._exchange_setup()[3]
+    g = torch.Generator(device="cuda")
+    g.manual_seed(6)
+    shape = (nz, ny, nx)
+    pa, pb = (torch.randn(shape, dtype=torch.complex128, device="cuda", generator=g) for _ in range(2))
+    acc = torch.zeros(shape, dtype=torch.complex128, device="cuda")
+    space = t.space_domain(sp.ProcessingUnit.GPU)
+
+    def call(unfused):
+        if not unfused:
+            return t.accumulate_fock(pa, pb, k, -1.0, acc, scaling=sp.Scaling.FULL)
+        torch.mul(pa.conj(), pb, out=space)  # the product written into the space domain
+        u = t.apply_reciprocal(k, scaling=sp.Scaling.FULL)
+        return acc.addcmul_(pa, u, value=-1.0)
+    rounds, calls = max(3, a.reps), 20
+    times = {"fused": [], "composed": []}
+    for unfused in (False, True):
+        call(unfused)
+    for _ in range(rounds):
+        for name, unfused in (("fused", False), ("composed", True)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                call(unfused)
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / calls)
+    med = {k_: sorted(v)[len(v) // 2] for k_, v in times.items()}
+    stages = {}
+    for name, unfused in (("fused", False), ("composed", True)):
+        sp.timing_reset()
+        sp.timing_enable(True)
+        try:
+            for _ in range(calls):
+                call(unfused)
+            t.synchronize()
+            torch.cuda.synchronize()
+            stages[name] = _gpu_stage_medians(sp.timing_json())
+        finally:
+            sp.timing_enable(False)
+    key = idx[:, 0].astype("int64") * (2 * ny + 1) + idx[:, 1]
+    sticks = len(set(key.tolist()))
+    columns = len(set(idx[:, 0].tolist()))
+    grid_bytes = nx * ny * nz * 16
+    # apply_reciprocal itself: the space domain read and written once, the [z][column][y]
+    # intermediate and the stick array written and read once per direction, K read
+    inter_bytes, stick_bytes = columns * ny * nz * 16, sticks * nz * 16
+    reciprocal = 2 * grid_bytes + 4 * inter_bytes + 4 * stick_bytes + len(idx) * 8
+    # composed: product (read 2, write 1) and addcmul_ (read 3, write 1) on top; fused: a
+    # and b instead of the space domain forward, a and acc read and acc written instead of
+    # the space domain backward
+    model_bytes = {"composed": reciprocal + 7 * grid_bytes, "fused": reciprocal + 3 * grid_bytes}
+    print(json.dumps({"workload": "plane-wave exchange pair", "fft_dims": list(basis.fft_dims),
+                      "num_values": len(idx), "sticks": sticks,
+                      "fock_fused": t.fock_fused, "reciprocal_fused": t.reciprocal_fused,
+                      "calls_per_s": {k_: 1.0 / v for k_, v in med.items()},
+                      "min_s": {k_: min(v) for k_, v in times.items()},
+                      "ratio_composed_over_fused": med["composed"] / med["fused"],
+                      "gpu_stage_median_s": stages,
+                      "model_bytes": model_bytes,
+                      "model_ratio": model_bytes["composed"] / model_bytes["fused"]}), flush=True)
 
 
 if __name__ == "__main__":
