@@ -144,7 +144,8 @@ SPFFT_EXPORT SpfftError spfft_amd_float_transform_backward_xy(SpfftFloatTransfor
  * input == output is allowed. After the call the contents of the space domain
  * are unspecified: fused plans (C2C transforms whose x lines fit one workgroup)
  * never form it and leave it untouched, other plans (R2C, long x lines) pass
- * through it. A null potential is SPFFT_INVALID_PARAMETER_ERROR. */
+ * through it. A null potential is SPFFT_INVALID_PARAMETER_ERROR, except on a
+ * rank without local planes, whose space domain is empty. */
 SPFFT_EXPORT SpfftError spfft_amd_transform_apply_local(SpfftTransform t, const double* input,
                                                         const double* potential, double* output,
                                                         SpfftScalingType scaling);

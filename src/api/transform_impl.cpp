@@ -106,7 +106,7 @@ void TransformImpl<T>::apply_local(const T* input, const T* potential, T* output
                                    SpfftScalingType scaling) {
   SPFFT_TIMED_SCOPE("apply_local");
   if (scaling != SPFFT_NO_SCALING && scaling != SPFFT_FULL_SCALING) throw InvalidParameterError();
-  if (!potential) throw InvalidParameterError();
+  if (!potential && plan_->local_planes() > 0) throw InvalidParameterError();
   backward_z(input);
   backward_exchange(false);
   apply_local_xy(potential);
@@ -117,7 +117,8 @@ void TransformImpl<T>::apply_local(const T* input, const T* potential, T* output
 
 template <typename T>
 void TransformImpl<T>::apply_local_xy(const T* potential) {
-  if (!potential) throw InvalidParameterError();
+  // (a rank without planes has an empty space domain and may pass no potential)
+  if (!potential && plan_->local_planes() > 0) throw InvalidParameterError();
   if (gpu_) {
     gpu_->apply_local_xy(potential);
     return;

@@ -419,6 +419,91 @@ def test_gpu_multi_transform_apply_local(gpu, batch):
     _subprocess_case("multi", {"SPFFT_BATCH": batch})
 
 
+# ---------------------------------------------- pinned cases of tools/fuzz_ops.py
+# The operator sweep (tests/test_fuzz_ops.py) reaches these by chance; here they always run:
+# its case runner on hand-written configurations (two calls against the dense oracle, the
+# inputs unchanged, a sentinel-filled space domain bit-identical on a fused plan), under the
+# sweep's bound of 1e-10.
+SKEWED = [((4, 32, 6), [1, 2, 1], [1, 0, 2]), ((3, 128, 4), [0, 1, 1], [1, 1, 0]),
+          ((2, 64, 5), [1, 0], [0, 1])]
+
+
+def _pinned(host=False, **choices):
+    import importlib.util
+    if "fuzz_ops" not in sys.modules:
+        spec = importlib.util.spec_from_file_location("fuzz_ops",
+                                                      os.path.join(REPO, "tools", "fuzz_ops.py"))
+        sys.modules["fuzz_ops"] = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(sys.modules["fuzz_ops"])
+    mod = sys.modules["fuzz_ops"]
+    desc, err, tol, facts = mod.run_case(mod.fixed_case("local", **choices), host=host)
+    print(desc, err, facts)
+    assert err < tol
+    return facts
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dims,sticks,planes", SKEWED)
+def test_gpu_unbuffered_skewed_distributions(gpu, dims, sticks, planes):
+    """UNBUFFERED (peer writes) on the skewed splits of test_gpu_transform's test of that
+    name: the y forward stage of the fused call stores through the remote column tables
+    while y backward reads the local ones; ranks without planes pass an empty potential."""
+    for f in _pinned(dims=dims, stick_dist=sticks, plane_dist=planes, exchange="UNBUFFERED"):
+        assert f["plan"][2] is True, f
+        assert f["fused"] is True and f["reciprocal_fused"] is False, f
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dims,sticks,planes", SKEWED)
+def test_gpu_compact_chunks_skewed_distributions(gpu, dims, sticks, planes):
+    """The same splits under the pipelined COMPACT_BUFFERED exchange, two plane chunks
+    forced: ranks with fewer planes than chunks run empty chunks."""
+    for f in _pinned(dims=dims, stick_dist=sticks, plane_dist=planes, chunks=2):
+        assert f["plan"][0] == 2 and f["plan"][2] is False, f
+        assert f["fused"] is True, f
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dims", [(16, 2048, 4), (4, 4, 4096)])
+def test_gpu_fused_beside_a_long_axis(gpu, dims):
+    """The fused x stage between four-step y passes, and behind a long z."""
+    (f,) = _pinned(dims=dims)
+    assert f["fused"] is True, f
+
+
+def test_host_rank_without_planes_passes_no_potential():
+    """A rank without local planes has an empty space domain: a null potential is accepted
+    there (a zero-element device tensor has a null address), and still refused on a rank
+    that holds planes. Found by tools/fuzz_ops.py."""
+    from spfft_amd.ops._lib import lib
+    from spfft_amd.parallel import run_ranks
+    from spfft_amd.types import ErrorCode
+    dims, sticks, planes = (2, 64, 5), [1.0, 0.0], [0, 5]
+    rng = np.random.default_rng(15)
+    parts = create_value_indices(rng, sticks, 0.9, 0.8, *dims, False)
+    ms = len(np.unique(parts[0][:, 0].astype(np.int64) * dims[1] + parts[0][:, 1]))
+    vals = _rand_vals(rng, len(parts[0]))
+    v = _potential(rng, dims)
+    want = _oracle(parts[0], vals, v, dims)
+    fn = lib().spfft_amd_transform_apply_local
+
+    def body(rank, comm):
+        grid = sp.Grid(*dims, ms, HOST, 1, max_local_z_length=5, comm=comm)
+        t = grid.create_transform(HOST, sp.TransformType.C2C, *dims, planes[rank], parts[rank])
+        mine = vals.copy() if rank == 0 else np.zeros(0, dtype=np.complex128)
+        out = np.zeros_like(mine)
+        refused = None
+        if rank == 1:  # checked before anything collective starts
+            refused = fn(t.handle, mine.ctypes.data, None, out.ctypes.data, 0)
+        code = fn(t.handle, mine.ctypes.data, None if rank == 0 else v.ctypes.data, out.ctypes.data, 0)
+        return code, refused, out
+
+    (code0, _, out0), (code1, refused1, _) = run_ranks(2, body)
+    assert code0 == 0 and code1 == 0
+    assert refused1 == int(ErrorCode.INVALID_PARAMETER)
+    assert max_rel_error(out0, want) < TOL64
+
+
 # ------------------------------------------------- cases run in their own process
 def _case_capped():
     import torch

@@ -492,6 +492,58 @@ def test_gpu_multi_transform_density_batched(gpu, nx, ny, single):
         assert err < (TOL32 if single else TOL64)
 
 
+# ---------------------------------------------- pinned cases of tools/fuzz_ops.py
+# The operator sweep (tests/test_fuzz_ops.py) reaches these by chance; here they always run:
+# its case runner on hand-written configurations (two calls, the whole rho and rho minus its
+# start against the dense oracle, the values unchanged, a sentinel-filled space domain
+# bit-identical on a fused plan), under the sweep's bound of 1e-10.
+SKEWED = [((4, 32, 6), [1, 2, 1], [1, 0, 2]), ((3, 128, 4), [0, 1, 1], [1, 1, 0]),
+          ((2, 64, 5), [1, 0], [0, 1])]
+
+
+def _pinned(**choices):
+    import importlib.util
+    if "fuzz_ops" not in sys.modules:
+        spec = importlib.util.spec_from_file_location("fuzz_ops",
+                                                      os.path.join(REPO, "tools", "fuzz_ops.py"))
+        sys.modules["fuzz_ops"] = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(sys.modules["fuzz_ops"])
+    mod = sys.modules["fuzz_ops"]
+    desc, err, tol, facts = mod.run_case(mod.fixed_case("density", **choices))
+    print(desc, err, facts)
+    assert err < tol
+    return facts
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dims,sticks,planes", SKEWED)
+def test_gpu_unbuffered_skewed_distributions(gpu, dims, sticks, planes):
+    """UNBUFFERED (peer writes) on the skewed splits of test_gpu_transform's test of that
+    name: the fused x density stage on a peer-written slab side; ranks without planes pass
+    an empty rho, ranks without sticks no values."""
+    for f in _pinned(dims=dims, stick_dist=sticks, plane_dist=planes, exchange="UNBUFFERED"):
+        assert f["plan"][2] is True, f
+        assert f["fused"] is True and f["reciprocal_fused"] is False, f
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dims,sticks,planes", SKEWED)
+def test_gpu_compact_chunks_skewed_distributions(gpu, dims, sticks, planes):
+    """The same splits under the pipelined COMPACT_BUFFERED exchange, two plane chunks
+    forced: ranks with fewer planes than chunks run empty chunks."""
+    for f in _pinned(dims=dims, stick_dist=sticks, plane_dist=planes, chunks=2):
+        assert f["plan"][0] == 2 and f["plan"][2] is False, f
+        assert f["fused"] is True, f
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dims", [(16, 2048, 4), (4, 4, 4096)])
+def test_gpu_fused_beside_a_long_axis(gpu, dims):
+    """The fused x stage after a four-step y pass, and behind a long z."""
+    (f,) = _pinned(dims=dims)
+    assert f["fused"] is True, f
+
+
 # ------------------------------------------------- cases run in their own process
 def _case_capped():
     import torch

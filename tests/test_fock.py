@@ -646,6 +646,65 @@ def test_host_exchange_operator():
         assert max_rel_error(p, q) < TOL64
 
 
+# ---------------------------------------------- pinned cases of tools/fuzz_ops.py
+# The operator sweep (tests/test_fuzz_ops.py) reaches these by chance; here they always run:
+# its case runner on hand-written configurations (two calls, the whole acc and acc minus its
+# start against the dense oracle, the values output, a, b and K unchanged, a sentinel-filled
+# space domain bit-identical on a fused plan), under the sweep's bound of 1e-10. Every stick
+# is full (z fill 1.0), so nothing but the exchange decides between the fused and the
+# composed z stage.
+SKEWED = [((4, 32, 6), [1, 2, 1], [1, 0, 2]), ((3, 128, 4), [0, 1, 1], [1, 1, 0]),
+          ((2, 64, 5), [1, 0], [0, 1])]
+
+
+def _pinned(**choices):
+    import importlib.util
+    if "fuzz_ops" not in sys.modules:
+        spec = importlib.util.spec_from_file_location("fuzz_ops",
+                                                      os.path.join(REPO, "tools", "fuzz_ops.py"))
+        sys.modules["fuzz_ops"] = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(sys.modules["fuzz_ops"])
+    mod = sys.modules["fuzz_ops"]
+    desc, err, tol, facts = mod.run_case(mod.fixed_case("fock", z_fill=1.0, **choices))
+    print(desc, err, facts)
+    assert err < tol
+    return facts
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dims,sticks,planes", SKEWED)
+def test_gpu_unbuffered_skewed_distributions(gpu, dims, sticks, planes):
+    """UNBUFFERED (peer writes) on the skewed splits of test_gpu_transform's test of that
+    name: the fused pair x stages on peer-written sides around the composed z stage; ranks
+    without planes pass empty a, b and acc, ranks without sticks an empty K and values."""
+    for f in _pinned(dims=dims, stick_dist=sticks, plane_dist=planes, exchange="UNBUFFERED"):
+        assert f["plan"][2] is True, f
+        assert f["fused"] is True and f["reciprocal_fused"] is False, f
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dims,sticks,planes", SKEWED)
+def test_gpu_compact_chunks_skewed_distributions(gpu, dims, sticks, planes):
+    """The same splits under the pipelined COMPACT_BUFFERED exchange, two plane chunks
+    forced: ranks with fewer planes than chunks run empty chunks, ranks without sticks
+    launch the fused z stage over an empty range."""
+    for f in _pinned(dims=dims, stick_dist=sticks, plane_dist=planes, chunks=2):
+        assert f["plan"][0] == 2 and f["plan"][2] is False, f
+        assert f["fused"] is True and f["reciprocal_fused"] is True, f
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dims,fused,zfused", [((16, 2048, 4), True, True), ((4, 4, 4096), True, None),
+                                               ((2048, 4, 16), False, True)])
+def test_gpu_beside_a_long_axis(gpu, dims, fused, zfused):
+    """The fused x stages between four-step y passes and behind a long z; the fused z stage
+    between composed x stages."""
+    (f,) = _pinned(dims=dims)
+    assert f["fused"] is fused, f
+    if zfused is not None:
+        assert f["reciprocal_fused"] is zfused, f
+
+
 # ------------------------------------------------- cases run in their own process
 def _case_capped():
     dims = (16, 16, 12)

@@ -577,6 +577,61 @@ def test_host_hartree_potential():
     assert a.dtype == np.float64 and max_rel_error(a, b) < TOL64
 
 
+# ---------------------------------------------- pinned cases of tools/fuzz_ops.py
+# The operator sweep (tests/test_fuzz_ops.py) reaches these by chance; here they always run:
+# its case runner on hand-written configurations (two calls against the dense oracle, the
+# values output, K and the input slab unchanged), under the sweep's bound of 1e-10. Every
+# stick is full (z fill 1.0), so nothing but the exchange decides between the fused and
+# the composed z stage. (apply_reciprocal has no fused x stage.)
+SKEWED = [((4, 32, 6), [1, 2, 1], [1, 0, 2]), ((3, 128, 4), [0, 1, 1], [1, 1, 0]),
+          ((2, 64, 5), [1, 0], [0, 1])]
+
+
+def _pinned(**choices):
+    import importlib.util
+    if "fuzz_ops" not in sys.modules:
+        spec = importlib.util.spec_from_file_location("fuzz_ops",
+                                                      os.path.join(REPO, "tools", "fuzz_ops.py"))
+        sys.modules["fuzz_ops"] = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(sys.modules["fuzz_ops"])
+    mod = sys.modules["fuzz_ops"]
+    desc, err, tol, facts = mod.run_case(mod.fixed_case("reciprocal", z_fill=1.0, **choices))
+    print(desc, err, facts)
+    assert err < tol
+    return facts
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dims,sticks,planes", SKEWED)
+def test_gpu_unbuffered_skewed_distributions(gpu, dims, sticks, planes):
+    """UNBUFFERED (peer writes) on the skewed splits of test_gpu_transform's test of that
+    name: forward and backward address a peer-written stick side differently, so the z
+    stage runs composed; ranks without sticks pass an empty K and values."""
+    for f in _pinned(dims=dims, stick_dist=sticks, plane_dist=planes, exchange="UNBUFFERED"):
+        assert f["plan"][2] is True, f
+        assert f["reciprocal_fused"] is False, f
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dims,sticks,planes", SKEWED)
+def test_gpu_compact_chunks_skewed_distributions(gpu, dims, sticks, planes):
+    """The same splits under the pipelined COMPACT_BUFFERED exchange, two plane chunks
+    forced: the fused z stage, ranks without sticks launch it over an empty range."""
+    for f in _pinned(dims=dims, stick_dist=sticks, plane_dist=planes, chunks=2):
+        assert f["plan"][0] == 2 and f["plan"][2] is False, f
+        assert f["reciprocal_fused"] is True, f
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dims,zfused", [((16, 2048, 4), True), ((4, 4, 4096), None),
+                                         ((2048, 4, 16), True)])
+def test_gpu_beside_a_long_axis(gpu, dims, zfused):
+    """The z stage beside four-step y passes and beside a long x; a long z itself."""
+    (f,) = _pinned(dims=dims)
+    if zfused is not None:
+        assert f["reciprocal_fused"] is zfused, f
+
+
 # ------------------------------------------------- cases run in their own process
 def _case_runtable():
     dims = (13, 5, 64)
