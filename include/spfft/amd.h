@@ -259,6 +259,33 @@ SPFFT_EXPORT SpfftError spfft_amd_float_transform_accumulate_fock(SpfftFloatTran
                                                                   int kernelIsComplex, float weight,
                                                                   float* acc, float* values,
                                                                   SpfftScalingType scaling);
+/* acc += sum_i weights[i] * a[i] * backward_i(K_i * (scale * forward_i(conj(a[i]) * b[i])))
+ * of n transforms (distinct grids, equal local space domains, all C2C or all
+ * R2C) into one shared acc: the pairs of one band of the exchange operator in
+ * one call. a[i], b[i] and acc are as in spfft_amd_transform_accumulate_fock;
+ * b[i] may be the same array for every i and may be a[i], acc overlapping any
+ * a or b is undefined. kernels[i] holds one entry per local value of transform
+ * i, all real or all interleaved complex (kernelIsComplex); the pointers may
+ * all be equal. One scaling for the call; there is no values output. All
+ * pointers are host or device pointers. Identical plans on one GPU with fused
+ * x and z stages and device pointers share one launch per stage, and the
+ * workgroup that owns a tile of acc adds the members' updates in list order
+ * (SPFFT_BATCH); everything else runs per transform with the phases
+ * interleaved. Every update of acc is ordered behind the previous one: the sum
+ * order is fixed by the call alone, the same call on the same data gives the
+ * same bits. Collective on distributed grids (per transform, in list order).
+ * A repeated grid, null transforms, a, b, kernels or weights with n > 0, a null
+ * acc, a[i] or b[i] with local planes, a null kernels[i] with local values,
+ * unequal space domains or a bad scaling is SPFFT_INVALID_PARAMETER_ERROR; the
+ * transforms stay usable. n == 0 is a no-op. */
+SPFFT_EXPORT SpfftError spfft_amd_multi_transform_accumulate_fock(
+    int n, SpfftTransform* transforms, const double* const* a, const double* const* b,
+    const double* const* kernels, int kernelIsComplex, const double* weights, double* acc,
+    SpfftScalingType scaling);
+SPFFT_EXPORT SpfftError spfft_amd_float_multi_transform_accumulate_fock(
+    int n, SpfftFloatTransform* transforms, const float* const* a, const float* const* b,
+    const float* const* kernels, int kernelIsComplex, const float* weights, float* acc,
+    SpfftScalingType scaling);
 /* *fused = 1 if the plan runs the fused pair x stages on the GPU, else 0. */
 SPFFT_EXPORT SpfftError spfft_amd_transform_fock_fused(SpfftTransform t, int* fused);
 SPFFT_EXPORT SpfftError spfft_amd_float_transform_fock_fused(SpfftFloatTransform t, int* fused);

@@ -763,3 +763,64 @@ def multi_transform_accumulate_density(transforms, inputs, weights, density):
     for t in transforms:
         t._step_keep = keeps
     return density
+
+
+def multi_transform_accumulate_fock(transforms, a, b, kernel, weights, acc, scaling=Scaling.NONE):
+    """acc += sum_i weights[i] * a[i] * backward_i(kernel_i * forward_i(conj(a[i]) * b[i],
+    scaling)) of several independent transforms (distinct grids, one space domain shape,
+    all C2C or all R2C) into one shared `acc`: the exchange pairs of one band in one call.
+    `a` and `b` hold one array per transform as in accumulate_fock (`b[i]` may be the same
+    array for every i, and may be `a[i]`); `kernel` is one array or tensor shared by all
+    transforms or a sequence of one per transform, all real or all complex. Identical
+    fused plans on one GPU share one launch per stage, and their updates of `acc` run
+    inside one workgroup per tile; the sum order is fixed by the call. Returns `acc`."""
+    n, prec, arr = _multi(transforms)
+    if len(a) != n or len(b) != n or len(weights) != n:
+        raise ValueError("one a, one b and one weight per transform")
+    if _is_torch(kernel) or isinstance(kernel, np.ndarray):
+        kernels = [kernel] * n
+    else:
+        kernels = list(kernel)
+        if len(kernels) != n:
+            raise ValueError("one kernel for all transforms, or one per transform")
+    if any(t._single != prec.single for t in transforms):
+        raise TypeError("transforms of one call share one precision")
+    shape = transforms[0].space_domain_shape() if n else None
+    if any(tuple(t.space_domain_shape()) != tuple(shape) for t in transforms):
+        raise ValueError("transforms of one call share one space domain shape")
+    real = transforms[0].type == TransformType.R2C if n else False
+    if any((t.type == TransformType.R2C) != real for t in transforms):
+        raise ValueError("transforms of one call are all C2C or all R2C")
+    if Scaling(scaling) not in (Scaling.NONE, Scaling.FULL):
+        raise ValueError(f"scaling: expected Scaling.NONE or Scaling.FULL, got {scaling}")
+    cptr, ckeep = _space_array_ptr(acc, prec, shape, real, "acc", True) if n else (None, None)
+    keeps = [ckeep]
+    aptrs, bptrs, kptrs = ((ctypes.c_void_p * max(1, n))() for _ in range(3))
+    cplx = None
+    for i, t in enumerate(transforms):
+        aptrs[i], akeep = _space_array_ptr(a[i], prec, shape, real, "a", False)
+        if b[i] is a[i]:
+            bptrs[i], bkeep = aptrs[i], akeep
+        elif i > 0 and b[i] is b[0]:
+            bptrs[i], bkeep = bptrs[0], None
+        else:
+            bptrs[i], bkeep = _space_array_ptr(b[i], prec, shape, real, "b", False)
+        if (i > 0 and kernels[i] is kernels[0]
+                and t.num_local_elements == transforms[0].num_local_elements):
+            kptrs[i], kkeep, c = kptrs[0], None, cplx  # one conversion, one pointer
+        else:
+            kptrs[i], kkeep, c = _kernel_ptr(kernels[i], prec, t.num_local_elements)
+        if cplx is None:
+            cplx = c
+        elif c != cplx:
+            raise TypeError("kernels of one call are all real or all complex")
+        keeps += [akeep, bkeep, kkeep]
+    ws = ((ctypes.c_float if prec.single else ctypes.c_double) * max(1, n))(
+        *[float(w) for w in weights])
+    _check(prec.amd_fn("multi_transform_accumulate_fock")(
+        n, arr, aptrs, bptrs, kptrs, 1 if cplx else 0, ctypes.cast(ws, ctypes.c_void_p), cptr,
+        int(scaling)))
+    # asynchronous execution (set_stream(..., synchronous=False)) may still use them
+    for t in transforms:
+        t._step_keep = keeps
+    return acc

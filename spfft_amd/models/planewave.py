@@ -12,7 +12,8 @@ per band are:
 Hybrid functionals add the exact-exchange operator, whose cost grows with the
 square of the number of occupied bands: per pair (a, b) a forward transform of
 conj(psi_a) psi_b, a multiply by K(G) and a backward transform, accumulated with
-psi_a (exchange_operator, one accumulate_fock call per pair).
+psi_a (exchange_operator, the pairs of a band in groups through
+multi_transform_accumulate_fock).
 
 Both run fully on the GPU with the space domain kept resident in the Grid's HBM
 slab, several bands at once through multi_transform.
@@ -243,18 +244,31 @@ class PlaneWaveModel:
     def exchange_kernel_host(self):
         return self._exchange_setup()[2]
 
+    def _exchange_transforms(self, count: int):
+        """The pair-density transform and `count` - 1 clones of it (made on first use)."""
+        tx = self._exchange_setup()[0]
+        clones = self.__dict__.setdefault("_exchange_clones", [])
+        while len(clones) < count - 1:
+            clones.append(tx.clone())
+        return [tx] + clones[:count - 1]
+
     def exchange_operator(self, psi: Sequence, occupations: Sequence[float],
-                          unfused: bool = False) -> List:
+                          unfused: bool = False, max_batch: int = 8) -> List:
         """Exact-exchange (Fock) operator of hybrid functionals on every band b, up to the
         cell-volume prefactor: the coefficients of
         sum_a -f_a psi_a(r) FFT^-1[ K(G) FFT[conj(psi_a) psi_b](G) ](r)
         over the occupied bands a (f_a != 0), projected back on the basis.
 
-        The bands go to real space once with the model's transforms; every pair (a, b)
-        is then one accumulate_fock call on the pair-density transform (on the GPU the
-        forward x stage forms conj(a) b in its loads, the backward x stage adds
-        -f_a a u to its rows of the accumulator from LDS, and no pair array goes through
-        memory); `unfused` runs the composition product, apply_reciprocal, addcmul."""
+        The bands go to real space once with the model's transforms; the pairs (a, b) of
+        a band b then go through multi_transform_accumulate_fock in groups of up to
+        `max_batch` occupied bands a, on the pair-density transform and its clones, into
+        the band's accumulator (a group of one is a plain accumulate_fock call). On the
+        GPU the forward x stage forms conj(a) b in its loads, the backward x stage adds
+        -f_a a u to its rows of the accumulator from LDS, no pair array goes through
+        memory, and a group shares one launch per stage; the sum over a runs in band
+        order whatever the grouping. `unfused` runs the composition product,
+        apply_reciprocal, addcmul, one pair at a time."""
+        from ..grid import multi_transform_accumulate_fock
         t0 = self.transforms[0]
         tx, _, _, k = self._exchange_setup()
         psi, occupations = list(psi), [float(f) for f in occupations]
@@ -263,13 +277,19 @@ class PlaneWaveModel:
             s = t0.backward(c)
             real.append(s.clone() if hasattr(s, "clone") else np.array(s))
         occupied = [(f, a) for f, a in zip(occupations, real) if f != 0.0]
+        step = max(1, int(max_batch))
+        groups = [occupied[g:g + step] for g in range(0, len(occupied), step)]
         out = []
         for b in real:
             acc = b.new_zeros(b.shape) if hasattr(b, "new_zeros") else np.zeros_like(b)
-            for f, a in occupied:
-                if not unfused:
-                    tx.accumulate_fock(a, b, k, -f, acc, scaling=Scaling.FULL)
-                    continue
+            for grp in ([] if unfused else groups):
+                if len(grp) == 1:
+                    tx.accumulate_fock(grp[0][1], b, k, -grp[0][0], acc, scaling=Scaling.FULL)
+                else:
+                    multi_transform_accumulate_fock(
+                        self._exchange_transforms(len(grp)), [a for _, a in grp], [b] * len(grp), k,
+                        [-f for f, _ in grp], acc, scaling=Scaling.FULL)
+            for f, a in (occupied if unfused else []):
                 # the product written straight into the space domain
                 space = tx.space_domain(self.pu)
                 if hasattr(acc, "addcmul_"):

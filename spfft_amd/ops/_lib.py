@@ -133,6 +133,8 @@ def _prototypes(lib):
     for pre, real in (("spfft_amd_", ctypes.c_double), ("spfft_amd_float_", ctypes.c_float)):
         sig[pre + "transform_accumulate_fock"] = [V, D, D, D, I, real, D, D, I]
         sig[pre + "transform_fock_fused"] = [V, c_int_p]
+        sig[pre + "multi_transform_accumulate_fock"] = [I, c_void_pp, c_void_pp, c_void_pp,
+                                                        c_void_pp, I, D, D, I]
     sig["spfft_amd_timing_enable"] = [I]
     sig["spfft_amd_timing_reset"] = []
     sig["spfft_amd_timing_json"] = [ctypes.c_char_p, ctypes.c_size_t, c_size_t_p]

@@ -43,6 +43,12 @@ void multi_accumulate_density_handles(int n, Transform** ts, const double* const
                                       const double* weights, double* density);
 void multi_accumulate_density_handles(int n, TransformFloat** ts, const float* const* in,
                                       const float* weights, float* density);
+void multi_accumulate_fock_handles(int n, Transform** ts, const double* const* a, const double* const* b,
+                                   const double* const* kernels, bool complexKernel, const double* weights,
+                                   double* acc, SpfftScalingType scaling);
+void multi_accumulate_fock_handles(int n, TransformFloat** ts, const float* const* a, const float* const* b,
+                                   const float* const* kernels, bool complexKernel, const float* weights,
+                                   float* acc, SpfftScalingType scaling);
 }  // namespace spfft
 
 using namespace spfft;
@@ -645,6 +651,32 @@ SpfftError spfft_amd_float_transform_accumulate_fock(SpfftFloatTransform t, cons
                                                      float* values, SpfftScalingType scaling) {
   return with_handle<TransformFloat>(t, [&](TransformFloat& x) {
     x.impl()->accumulate_fock(a, b, kernel, kernelIsComplex != 0, weight, acc, values, scaling);
+  });
+}
+SpfftError spfft_amd_multi_transform_accumulate_fock(int n, SpfftTransform* transforms,
+                                                     const double* const* a, const double* const* b,
+                                                     const double* const* kernels, int kernelIsComplex,
+                                                     const double* weights, double* acc,
+                                                     SpfftScalingType scaling) {
+  if (n > 0 && !transforms) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < n; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_accumulate_fock_handles(n, reinterpret_cast<Transform**>(transforms), a, b, kernels,
+                                  kernelIsComplex != 0, weights, acc, scaling);
+  });
+}
+SpfftError spfft_amd_float_multi_transform_accumulate_fock(int n, SpfftFloatTransform* transforms,
+                                                           const float* const* a, const float* const* b,
+                                                           const float* const* kernels,
+                                                           int kernelIsComplex, const float* weights,
+                                                           float* acc, SpfftScalingType scaling) {
+  if (n > 0 && !transforms) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < n; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_accumulate_fock_handles(n, reinterpret_cast<TransformFloat**>(transforms), a, b, kernels,
+                                  kernelIsComplex != 0, weights, acc, scaling);
   });
 }
 SpfftError spfft_amd_transform_fock_fused(SpfftTransform t, int* fused) {

@@ -271,6 +271,96 @@ void multi_accumulate_density(const std::vector<TransformImpl<T>*>& ts, const T*
     if (ts[i]->is_gpu() && ts[i]->gpu()->synchronous()) ts[i]->synchronize();
 }
 
+// acc += sum_i weights[i] a[i] backward_i(K_i (scale forward_i(conj(a[i]) b[i]))) into
+// one shared acc: the pairs of one band of the exchange operator. Plans with
+// fused x and z stages and equal keys run as batches first (in group order),
+// everything else per transform with the phases interleaved, in list order.
+// Every update of acc is ordered behind the previous one as in
+// multi_accumulate_density (`last`), so the sum order depends on the call alone.
+// A host acc is staged by each GPU member in its own buffer: such members run
+// strictly one after another, each behind a synchronize of the previous one, so
+// that no staged copy is written back over a later update.
+template <typename T>
+void multi_accumulate_fock(const std::vector<TransformImpl<T>*>& ts, const T* const* a, const T* const* b,
+                           const T* const* kernels, bool complexKernel, const T* weights, T* acc,
+                           SpfftScalingType scaling) {
+  SPFFT_TIMED_SCOPE("multi_accumulate_fock");
+  check_distinct_grids(ts);
+  const int n = static_cast<int>(ts.size());
+  if (n > 0 && (!a || !b || !kernels || !weights)) throw InvalidParameterError();
+  if (scaling != SPFFT_NO_SCALING && scaling != SPFFT_FULL_SCALING) throw InvalidParameterError();
+  for (int i = 0; i < n; ++i) {
+    const IndexPlan& p = ts[i]->plan();
+    const IndexPlan& p0 = ts[0]->plan();
+    // one acc: one local space domain, complex or real
+    if (p.type != p0.type || p.dimX != p0.dimX || p.dimY != p0.dimY || p.local_planes() != p0.local_planes())
+      throw InvalidParameterError();
+    if (p.local_planes() > 0 && (!acc || !a[i] || !b[i])) throw InvalidParameterError();
+    if (p.numLocalElements > 0 && !kernels[i]) throw InvalidParameterError();
+  }
+  GpuExecutor<T>* last = nullptr;
+  const bool deviceAcc = acc && is_device_pointer(acc);
+  const std::vector<bool> batched = run_batches<T>(
+      ts,
+      [&](int i) {
+        const IndexPlan& p = ts[i]->plan();
+        return ts[i]->fock_fused() && ts[i]->reciprocal_fused() && deviceAcc &&
+               (p.local_planes() == 0 || (is_device_pointer(a[i]) && is_device_pointer(b[i]))) &&
+               (p.numLocalElements == 0 || is_device_pointer(kernels[i]));
+      },
+      [](int) { return 0; },
+      [&](const std::vector<int>& g) {
+        std::vector<GpuExecutor<T>*> ex;
+        std::vector<const T*> as, bs, ks;
+        std::vector<T> ws;
+        for (int j : g) {
+          ex.push_back(ts[j]->gpu());
+          as.push_back(a[j]);
+          bs.push_back(b[j]);
+          ks.push_back(kernels[j]);
+          ws.push_back(weights[j]);
+        }
+        GpuExecutor<T>::accumulate_fock_batch(ex, as, bs, ks, complexKernel, ws, acc, scaling, last);
+        last = ex[0];
+      });
+  for (int i = 0; i < n; ++i)
+    if (ts[i]->is_gpu() && !batched[i]) ts[i]->fock_forward_xy(a[i], b[i]);
+  for (int i = 0; i < n; ++i)
+    if (!ts[i]->is_gpu()) {
+      ts[i]->fock_forward_xy(a[i], b[i]);
+      ts[i]->forward_exchange(true);
+    }
+  for (int i = 0; i < n; ++i)
+    if (ts[i]->is_gpu() && !batched[i]) {
+      ts[i]->forward_exchange(true);
+      ts[i]->reciprocal_z(kernels[i], complexKernel, nullptr, scaling);
+    }
+  for (int i = 0; i < n; ++i)
+    if (!ts[i]->is_gpu()) {
+      ts[i]->reciprocal_z(kernels[i], complexKernel, nullptr, scaling);
+      ts[i]->backward_exchange(true);
+    }
+  for (int i = 0; i < n; ++i)
+    if (ts[i]->is_gpu() && !batched[i]) {
+      ts[i]->backward_exchange(true);
+      if (!deviceAcc && last) {
+        last->synchronize();  // its copy of acc is back on the host
+        last = nullptr;
+      }
+      ts[i]->gpu()->fock_backward_xy(a[i], acc, weights[i], last);
+      last = ts[i]->gpu();
+    }
+  for (int i = 0; i < n; ++i)
+    if (!ts[i]->is_gpu()) {
+      // a host transform updates acc on the calling thread: behind the GPU transforms' updates
+      if (last) last->synchronize();
+      last = nullptr;
+      ts[i]->fock_backward_xy(a[i], acc, weights[i]);
+    }
+  for (int i = 0; i < n; ++i)
+    if (ts[i]->is_gpu() && ts[i]->gpu()->synchronous()) ts[i]->synchronize();
+}
+
 template <typename TR, typename T>
 std::vector<TransformImpl<T>*> impls(int n, TR* transforms) {
   if (n < 0 || (n > 0 && !transforms)) throw InvalidParameterError();
@@ -348,6 +438,22 @@ void multi_accumulate_density_handles(int n, TransformFloat** ts, const float* c
   std::vector<TransformImpl<float>*> v;
   for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
   multi_accumulate_density<float>(v, in, weights, density);
+}
+void multi_accumulate_fock_handles(int n, Transform** ts, const double* const* a, const double* const* b,
+                                   const double* const* kernels, bool complexKernel, const double* weights,
+                                   double* acc, SpfftScalingType scaling) {
+  if (n < 0 || (n > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<double>*> v;
+  for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_accumulate_fock<double>(v, a, b, kernels, complexKernel, weights, acc, scaling);
+}
+void multi_accumulate_fock_handles(int n, TransformFloat** ts, const float* const* a, const float* const* b,
+                                   const float* const* kernels, bool complexKernel, const float* weights,
+                                   float* acc, SpfftScalingType scaling) {
+  if (n < 0 || (n > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<float>*> v;
+  for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_accumulate_fock<float>(v, a, b, kernels, complexKernel, weights, acc, scaling);
 }
 void multi_forward_handles(int n, TransformFloat** ts, SpfftProcessingUnitType* in, float** out,
                            SpfftScalingType* sc) {

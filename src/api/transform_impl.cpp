@@ -224,42 +224,57 @@ void TransformImpl<T>::accumulate_fock(const T* a, const T* b, const T* kernel, 
   const std::size_t space = static_cast<std::size_t>(p.local_planes()) * p.dimY * p.dimX;
   if (space > 0 && (!a || !b || !acc)) throw InvalidParameterError();
   if (!kernel && p.numLocalElements > 0) throw InvalidParameterError();
-  const bool real = p.type == SPFFT_TRANS_R2C;
-  if (gpu_) {
-    gpu_->fock_forward_xy(a, b);
-  } else {
-    // host: the plain composition through the space domain
-    T* s = host_->space_domain();
-    if (real) {
-      for (std::size_t i = 0; i < space; ++i) s[i] = a[i] * b[i];
-    } else {
-      for (std::size_t i = 0; i < space; ++i) {
-        const T ar = a[2 * i], ai = a[2 * i + 1], br = b[2 * i], bi = b[2 * i + 1];
-        s[2 * i] = ar * br + ai * bi;
-        s[2 * i + 1] = ar * bi - ai * br;
-      }
-    }
-    host_->forward_xy();
-  }
+  fock_forward_xy(a, b);
   forward_exchange(false);
   reciprocal_z(kernel, complexKernel, values, scaling);
   backward_exchange(false);
+  fock_backward_xy(a, acc, weight);
+  if (gpu_ && gpu_->synchronous()) gpu_->synchronize();
+}
+
+// the stages of accumulate_fock in front of forward_exchange and behind
+// backward_exchange (multi-transform interleaving)
+template <typename T>
+void TransformImpl<T>::fock_forward_xy(const T* a, const T* b) {
   if (gpu_) {
-    gpu_->fock_backward_xy(a, acc, weight);
+    gpu_->fock_forward_xy(a, b);
+    return;
+  }
+  // host: the plain composition through the space domain
+  const IndexPlan& p = *plan_;
+  const std::size_t space = static_cast<std::size_t>(p.local_planes()) * p.dimY * p.dimX;
+  T* s = host_->space_domain();
+  if (p.type == SPFFT_TRANS_R2C) {
+    for (std::size_t i = 0; i < space; ++i) s[i] = a[i] * b[i];
   } else {
-    host_->backward_xy();
-    const T* u = host_->space_domain();
-    if (real) {
-      for (std::size_t i = 0; i < space; ++i) acc[i] += weight * a[i] * u[i];
-    } else {
-      for (std::size_t i = 0; i < space; ++i) {
-        const T tr = weight * a[2 * i], ti = weight * a[2 * i + 1];
-        acc[2 * i] += tr * u[2 * i] - ti * u[2 * i + 1];
-        acc[2 * i + 1] += tr * u[2 * i + 1] + ti * u[2 * i];
-      }
+    for (std::size_t i = 0; i < space; ++i) {
+      const T ar = a[2 * i], ai = a[2 * i + 1], br = b[2 * i], bi = b[2 * i + 1];
+      s[2 * i] = ar * br + ai * bi;
+      s[2 * i + 1] = ar * bi - ai * br;
     }
   }
-  if (gpu_ && gpu_->synchronous()) gpu_->synchronize();
+  host_->forward_xy();
+}
+
+template <typename T>
+void TransformImpl<T>::fock_backward_xy(const T* a, T* acc, T weight) {
+  if (gpu_) {
+    gpu_->fock_backward_xy(a, acc, weight);
+    return;
+  }
+  const IndexPlan& p = *plan_;
+  const std::size_t space = static_cast<std::size_t>(p.local_planes()) * p.dimY * p.dimX;
+  host_->backward_xy();
+  const T* u = host_->space_domain();
+  if (p.type == SPFFT_TRANS_R2C) {
+    for (std::size_t i = 0; i < space; ++i) acc[i] += weight * a[i] * u[i];
+  } else {
+    for (std::size_t i = 0; i < space; ++i) {
+      const T tr = weight * a[2 * i], ti = weight * a[2 * i + 1];
+      acc[2 * i] += tr * u[2 * i] - ti * u[2 * i + 1];
+      acc[2 * i + 1] += tr * u[2 * i + 1] + ti * u[2 * i];
+    }
+  }
 }
 
 template <typename T>

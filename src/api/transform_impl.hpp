@@ -60,6 +60,12 @@ public:
   void accumulate_fock(const T* a, const T* b, const T* kernel, bool complexKernel, T weight, T* acc,
                        T* values, SpfftScalingType scaling);
   bool fock_fused() const { return gpu_ && gpu_->fock_fused(); }
+  // the stages of accumulate_fock around the two exchanges (multi-transform
+  // interleaving): fock_forward_xy, forward_exchange, reciprocal_z,
+  // backward_exchange, fock_backward_xy
+  void fock_forward_xy(const T* a, const T* b);
+  void reciprocal_z(const T* kernel, bool complexKernel, T* values, SpfftScalingType scaling);
+  void fock_backward_xy(const T* a, T* acc, T weight);
 
   void forward_xy(SpfftProcessingUnitType inputLocation);
   void forward_exchange(bool nonBlocking);
@@ -81,7 +87,6 @@ public:
 
 private:
   void create_executor();
-  void reciprocal_z(const T* kernel, bool complexKernel, T* values, SpfftScalingType scaling);
 
   std::shared_ptr<GridImpl<T>> grid_;
   SpfftProcessingUnitType exec_;

@@ -1560,7 +1560,7 @@ void GpuExecutor<T>::fock_forward_xy(const T* a, const T* b) {
 }
 
 template <typename T>
-void GpuExecutor<T>::fock_backward_xy(const T* a, T* acc, T weight) {
+void GpuExecutor<T>::fock_backward_xy(const T* a, T* acc, T weight, GpuExecutor* after) {
   SPFFT_TIMED_SCOPE("gpu_fock_backward_xy");
   DeviceGuard guard(deviceId_);
   const IndexPlan& p = *plan_;
@@ -1575,16 +1575,21 @@ void GpuExecutor<T>::fock_backward_xy(const T* a, T* acc, T weight) {
   if (staged) {
     if (!fockAcc_ || fockAcc_->bytes() < bytes) fockAcc_.reset(new DeviceBuffer(bytes));
     dacc = fockAcc_->data<T>();
+    order_after_density(after);  // its download of this acc
+    after = nullptr;
     gpu_check(hipMemcpyAsync(dacc, acc, bytes, hipMemcpyHostToDevice, stream_), "hipMemcpyAsync");
   }
   if (!fockFused_) {
     backward_xy(SPFFT_PU_GPU);
+    order_after_density(after);
     dev::launch_space_fock<T>(grid_->device_slot(GridImpl<T>::kSpace), da, dacc, weight,
                               static_cast<long long>(count), real, stream_);
     stage_mark("backward", "fock");
   } else {
     StageEnd stageEnd{this, "backward", pipelined() ? "exchange+y+x_fock" : "y+x_fock"};
     backward_yx_ranges([&](const dev::XArgs& xa, cx<T>* tile) {
+      order_after_density(after);  // (once: the stream stays behind it)
+      after = nullptr;
       dev::launch_x_backward_fock<T>(xa, tile, reinterpret_cast<const cx<T>*>(da), reinterpret_cast<cx<T>*>(dacc),
                                      weight, twX_->data<cx<T>>(), stream_);
     });
@@ -1897,6 +1902,85 @@ void GpuExecutor<T>::accumulate_density_batch(const std::vector<GpuExecutor*>& e
   l->order_after_density(after);
   dev::launch_x_density<T>(xa, static_cast<const cx<T>*>(xb.in[0]), density, weights.data(),
                            l->twX_->data<cx<T>>(), s);
+  batch_release(ex);
+}
+
+// One launch per stage for a batch of plans with fused pair x stages and a fused
+// z stage that accumulate into one acc: x forward pair, y forward, z reciprocal
+// (in place on the members' stick sides), y backward, then one accumulating x
+// launch whose workgroups loop over the members for their tile of acc (the
+// members share acc, so they are not spread over the grid). A b shared by the
+// whole batch is read with the default cache policy.
+template <typename T>
+void GpuExecutor<T>::accumulate_fock_batch(const std::vector<GpuExecutor*>& ex, const std::vector<const T*>& a,
+                                           const std::vector<const T*>& b,
+                                           const std::vector<const T*>& kernels, bool complexKernel,
+                                           const std::vector<T>& weights, T* acc, SpfftScalingType scaling,
+                                           GpuExecutor* after) {
+  SPFFT_TIMED_SCOPE("gpu_accumulate_fock_batch");
+  const int n = static_cast<int>(ex.size());
+  if (n < 1 || n > dev::kMaxBatch || a.size() != ex.size() || b.size() != ex.size() ||
+      kernels.size() != ex.size() || weights.size() != ex.size())
+    throw InternalError();
+  GpuExecutor* l = ex[0];
+  DeviceGuard guard(l->deviceId_);
+  for (GpuExecutor* e : ex)
+    if (!e->batchable() || !e->fockFused_ || !e->reciprocalFused_ || e->batchKey_ != l->batchKey_)
+      throw InternalError();
+  const IndexPlan& p = *l->plan_;
+  const bool planes = p.local_planes() > 0;
+  if (planes && (!acc || !is_device_pointer(acc))) throw InvalidParameterError();
+  const T factor = scaling == SPFFT_FULL_SCALING
+                       ? static_cast<T>(1.0 / (static_cast<double>(p.dimX) * p.dimY * p.dimZ))
+                       : T(1);
+  dev::BatchPtrs xf{}, yf{}, zr{}, yb{}, xb{};
+  xf.count = yf.count = zr.count = yb.count = xb.count = n;
+  std::vector<const cx<T>*> pa(n), pb(n);
+  bool shared = true;
+  for (int i = 0; i < n; ++i) {
+    GpuExecutor* e = ex[i];
+    if (planes && (!a[i] || !is_device_pointer(a[i]) || !b[i] || !is_device_pointer(b[i])))
+      throw InvalidParameterError();
+    if (p.numLocalElements > 0 && (!kernels[i] || !is_device_pointer(kernels[i])))
+      throw InvalidParameterError();
+    shared = shared && b[i] == b[0];
+    pa[i] = reinterpret_cast<const cx<T>*>(a[i]);
+    pb[i] = reinterpret_cast<const cx<T>*>(b[i]);
+    void* stick = e->grid_->device_slot(GridImpl<T>::kStickSide);
+    void* slab = e->grid_->device_slot(GridImpl<T>::kSlabSide);
+    void* inter = e->grid_->device_slot(GridImpl<T>::kInter);
+    xf.in[i] = a[i];
+    xf.out[i] = inter;
+    yf.in[i] = inter;
+    yf.out[i] = slab;
+    zr.in[i] = kernels[i];
+    zr.out[i] = stick;
+    yb.in[i] = slab;
+    yb.out[i] = inter;
+    xb.in[i] = inter;
+    xb.out[i] = nullptr;  // the members share `acc`
+  }
+  batch_join(ex);
+  auto za = l->zargs();
+  auto ya = l->yargs();
+  auto xa = l->xargs();
+  hipStream_t s = l->stream_;
+  xa.batch = xf;
+  dev::launch_x_forward_pair_batch<T>(xa, pb.data(), shared, l->twX_->data<cx<T>>(), s);
+  ya.batch = yf;
+  dev::launch_y_forward<T, cx<T>>(ya, static_cast<const cx<T>*>(yf.in[0]), static_cast<cx<T>*>(yf.out[0]),
+                                  l->twY_->data<cx<T>>(), s);
+  za.batch = zr;
+  za.plainSticks = l->plainHandoff_;
+  dev::launch_z_reciprocal_batch<T>(za, complexKernel, factor, l->twZ_->data<cx<T>>(), s);
+  ya.batch = yb;
+  ya.plainSticks = l->plainHandoff_;
+  dev::launch_y_backward<T, cx<T>>(ya, static_cast<const cx<T>*>(yb.in[0]), static_cast<cx<T>*>(yb.out[0]),
+                                   l->twY_->data<cx<T>>(), s);
+  l->order_after_density(after);
+  xa.batch = xb;
+  dev::launch_x_backward_fock_batch<T>(xa, pa.data(), weights.data(), reinterpret_cast<cx<T>*>(acc),
+                                       l->twX_->data<cx<T>>(), s);
   batch_release(ex);
 }
 

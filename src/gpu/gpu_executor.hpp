@@ -115,9 +115,18 @@ public:
   // inverse x FFT from LDS) and leave the space domain untouched; other plans
   // run space = conj(a) * b, forward_xy and backward_xy, acc += weight * a *
   // space. fock_backward_xy takes the `a` given to fock_forward_xy.
+  // `after`: the executor whose stream holds the latest update of this acc
+  // (multi-transform calls); the update is ordered behind it.
   void fock_forward_xy(const T* a, const T* b);
-  void fock_backward_xy(const T* a, T* acc, T weight);
+  void fock_backward_xy(const T* a, T* acc, T weight, GpuExecutor* after = nullptr);
   bool fock_fused() const { return fockFused_; }
+  // batchable() plans with fused x and z stages and equal keys into one acc:
+  // one launch per stage on the leader's stream, the accumulating x workgroups
+  // loop over the members in order (device pointers)
+  static void accumulate_fock_batch(const std::vector<GpuExecutor*>& ex, const std::vector<const T*>& a,
+                                    const std::vector<const T*>& b, const std::vector<const T*>& kernels,
+                                    bool complexKernel, const std::vector<T>& weights, T* acc,
+                                    SpfftScalingType scaling, GpuExecutor* after = nullptr);
 
   void synchronize();
   bool synchronous() const { return synchronous_; }

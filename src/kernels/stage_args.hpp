@@ -187,6 +187,21 @@ void launch_x_forward_pair(const XArgs& a, const cx<T>* pa, const cx<T>* pb, cx<
 template <typename T>
 void launch_x_backward_fock(const XArgs& a, const cx<T>* inter, const cx<T>* pa, cx<T>* acc, T weight,
                             const cx<T>* tw, hipStream_t stream);
+// Batched pair operator (multi_transform_accumulate_fock), one launch per stage
+// for batch.count members with identical plans. Forward x: member m's a is
+// XArgs::batch.in[m], its b is pb[m], its intermediate batch.out[m]. z stage:
+// member m's stick array (in place) is ZArgs::batch.out[m], its kernel K
+// batch.in[m]; no values output. Backward x: the members share acc, so every
+// workgroup loops over them for its tile, in member order (intermediates
+// batch.in[m], pa[m], weights[m]; the grid is the unbatched grid).
+template <typename T>
+void launch_x_forward_pair_batch(const XArgs& a, const cx<T>* const* pb, bool plainLoads, const cx<T>* tw,
+                                 hipStream_t stream);
+template <typename T>
+void launch_z_reciprocal_batch(const ZArgs& a, bool complexKernel, T scale, const cx<T>* tw, hipStream_t stream);
+template <typename T>
+void launch_x_backward_fock_batch(const XArgs& a, const cx<T>* const* pa, const T* weights, cx<T>* acc,
+                                  const cx<T>* tw, hipStream_t stream);
 // Composed path, one pass each: space[i] = conj(a[i]) * b[i] and acc[i] +=
 // weight * a[i] * space[i] (interleaved complex or, realSpace, real arrays).
 template <typename T>

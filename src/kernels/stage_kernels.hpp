@@ -1527,6 +1527,73 @@ __global__ void __launch_bounds__(Eng::kBlock)
   });
 }
 
+// Batched launch of the kernel above (the pairs of
+// multi_transform_accumulate_fock): blockIdx.z selects the member, whose stick
+// array (in place) is ZArgs::batch.out and whose kernel K is ZArgs::batch.in;
+// the index tables are shared, and there is no values output. A kernel of its
+// own, not a shared inlined body: with the body in a function the single
+// launch's kernels took 12 to 42 more VGPRs (N = 128 fp64: 86 -> 128).
+template <class Eng, class Fwd, typename T, bool Cplx, bool Plain>
+__global__ void __launch_bounds__(Eng::kBlock)
+    z_reciprocal_batch_kernel(Eng eng, Fwd fwd, ZArgs a, T scale, const cx<T>* __restrict__ tw) {
+  SPFFT_LDS_DECL(T);
+  cx<T>* sticks = static_cast<cx<T>*>(a.batch.out[blockIdx.z]);
+  const T* __restrict__ kern = static_cast<const T*>(a.batch.in[blockIdx.z]);
+  const int B = eng.lines();
+  const int n = eng.n();
+  const int s0 = a.stickBegin + block_tile_x() * B;
+  const int nl = min(B, a.numSticks - s0);
+  const ZSeg seg(a.single, a.stickStride, a.zTab,
+                 reinterpret_cast<char*>(lds) + zseg_lds_offset(eng.lds_bytes(), B), n);
+  StickDesc* d = reinterpret_cast<StickDesc*>(reinterpret_cast<char*>(lds) + eng.lds_bytes());
+  for (int b = threadIdx.x; b < nl; b += blockDim.x) d[b] = a.desc[s0 + b];
+  // result at fwd.out_at(b, z); ends with a barrier (which also publishes d)
+  fwd.global_to_lds(lds, tw, [&](int b, int pos) -> cx<T> {
+    if (b >= nl) return czero<T>();
+    return ld_stream(&sticks[seg.at(s0 + b, pos)]);
+  });
+  const int total = B * n;
+  for (int base = threadIdx.x; base < total; base += blockDim.x * kApplyUnroll) {
+    cx<T> w[kApplyUnroll];
+    int vi[kApplyUnroll];
+#pragma unroll
+    for (int u = 0; u < kApplyUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      vi[u] = -1;
+      if (idx < total) {
+        const int b = idx / n, z = idx - b * n;
+        if (b < nl) {
+          const StickDesc& q = d[b];
+          const int j = desc_offset(q, z);
+          if (j >= 0) {
+            vi[u] = q.valueStart + j;
+            w[u] = ld_kernel<T, Cplx>(kern, vi[u]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kApplyUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        const int b = idx / n, z = idx - b * n;
+        cx<T> r = czero<T>();
+        if (vi[u] >= 0) {
+          const cx<T> v = spfft::scale(lds[fwd.out_at(b, z)], scale);
+          if constexpr (Cplx) r = cmul(v, w[u]);
+          else r = spfft::scale(v, w[u].x);
+        }
+        lds[eng.in_at(b, z)] = r;
+      }
+    }
+  }
+  __syncthreads();
+  if (a.zeroStick >= s0 && a.zeroStick < s0 + nl) hermitian_lines_inline(eng, lds, a.zeroStick - s0, 1, n);
+  eng.lds_to_global(lds, tw, [&](int b, int pos, cx<T> v) {
+    if (b < nl) st_stick<Plain>(&sticks[seg.at(s0 + b, pos)], v);
+  });
+}
+
 // out[i] = in[i] * K[i] over `count` sparse values (the composed reciprocal-space
 // operator path; out may be in); K real or complex.
 template <typename T, bool Cplx>
@@ -1719,9 +1786,9 @@ __global__ void __launch_bounds__(256)
 // their loads (a template parameter: a run-time flag costs registers and can
 // lose the hint, profiles/r6/ntmerge). a may be b: both are only read.
 template <class Eng, typename T, bool StreamAB>
-__global__ void __launch_bounds__(Eng::kBlock)
-    x_forward_pair_kernel(Eng eng, XArgs a, const cx<T>* __restrict__ pa, const cx<T>* __restrict__ pb,
-                          cx<T>* __restrict__ inter, const cx<T>* __restrict__ tw) {
+__device__ __forceinline__ void x_forward_pair_body(const Eng& eng, const XArgs& a, const cx<T>* __restrict__ pa,
+                                                    const cx<T>* __restrict__ pb, cx<T>* __restrict__ inter,
+                                                    const cx<T>* __restrict__ tw) {
   SPFFT_LDS_DECL(T);
   const int B = eng.lines();
   const int n = eng.n();
@@ -1743,6 +1810,35 @@ __global__ void __launch_bounds__(Eng::kBlock)
   };
   stage_rows(eng, lds, yl, n, PairSrc<T, StreamAB>{{pa + row0, pb + row0}, n});
   eng.lds_to_global(lds, tw, store);
+}
+
+template <class Eng, typename T, bool StreamAB>
+__global__ void __launch_bounds__(Eng::kBlock)
+    x_forward_pair_kernel(Eng eng, XArgs a, const cx<T>* __restrict__ pa, const cx<T>* __restrict__ pb,
+                          cx<T>* __restrict__ inter, const cx<T>* __restrict__ tw) {
+  x_forward_pair_body<Eng, T, StreamAB>(eng, a, pa, pb, inter, tw);
+}
+
+// Per-member arguments of the batched pair launches that BatchPtrs has no room
+// for, by value (as DensityWeights): the second input of the forward stage; the
+// `a` arrays and weights of the accumulating backward stage.
+template <typename T>
+struct PairSecond {
+  const cx<T>* b[kMaxBatch];
+};
+template <typename T>
+struct FockMembers {
+  const cx<T>* a[kMaxBatch];
+  T w[kMaxBatch];
+};
+
+// Batched launch: blockIdx.z selects the member, whose a is XArgs::batch.in,
+// whose b is second.b and whose intermediate is XArgs::batch.out.
+template <class Eng, typename T, bool StreamAB>
+__global__ void __launch_bounds__(Eng::kBlock)
+    x_forward_pair_batch_kernel(Eng eng, XArgs a, PairSecond<T> second, const cx<T>* __restrict__ tw) {
+  x_forward_pair_body<Eng, T, StreamAB>(eng, a, static_cast<const cx<T>*>(a.batch.in[blockIdx.z]),
+                                        second.b[blockIdx.z], static_cast<cx<T>*>(a.batch.out[blockIdx.z]), tw);
 }
 
 // acc[idx] += w a[idx] lds[src(idx)] for idx in [0, total): lanes walk the rows
@@ -1819,6 +1915,66 @@ __global__ void __launch_bounds__(Eng::kBlock)
     return eng.out_at(b, idx - b * n);
   });
 }
+
+// The pairs of a batched launch share acc, so they are not spread over
+// blockIdx.z: the workgroup that owns a tile loops over the members in order
+// (intermediates from XArgs::batch.in, a and weight from `members`), as
+// x_density_kernel does over its bands. Lane idx updates the same elements of
+// acc for every member, so a member's update is ordered behind the previous
+// one's by the lane's own program order: the sum order is fixed, without
+// atomics. The members revisit the tile of acc, so its accesses (and those of
+// a) take the default cache policy.
+template <class Eng, typename T>
+__global__ void __launch_bounds__(Eng::kBlock)
+    x_backward_fock_batch_kernel(Eng eng, XArgs a, FockMembers<T> members, cx<T>* __restrict__ acc,
+                                 const cx<T>* __restrict__ tw) {
+  SPFFT_LDS_DECL(T);
+  const int B = eng.lines();
+  const int n = eng.n();
+  int tx, ty;
+  block_tile(tx, ty);
+  const int zl = a.zBegin + ty;
+  const int y0 = tx * B;
+  int* xCol = reinterpret_cast<int*>(reinterpret_cast<char*>(lds) + eng.lds_bytes());
+  build_xcol(a, xCol, n);
+  const int yl = min(B, a.Y - y0);
+  const long long row0 = (static_cast<long long>(zl) * a.Y + y0) * n;
+  for (int m = 0; m < a.batch.count; ++m) {
+    // the per-element arguments and the twiddle table are pinned anew for every
+    // member: as loop invariants they were hoisted out of the loop and stayed
+    // live across it (see x_density_kernel)
+    const cx<T>* twM = reinterpret_cast<const cx<T>*>(pin_uniform64(reinterpret_cast<long long>(tw)));
+    const int rowStride = pin_uniform(static_cast<int>(a.interStride)), nFreq = pin_uniform(a.nFreq);
+    const int dense = pin_uniform(x_dense(a) ? 1 : 0);
+    auto col_of = [&](int x) { return dense ? (x < nFreq ? x : -1) : xCol[x]; };
+    const cx<T>* src = static_cast<const cx<T>*>(a.batch.in[m]) + static_cast<long long>(zl) * a.interZStride + y0;
+    auto load = [&](int b, int pos) -> cx<T> {
+      if (b >= yl) return czero<T>();
+      const int c = col_of(pos);
+      return c < 0 ? czero<T>() : ld_inter(&src[c * rowStride + b]);
+    };
+    if (m > 0) __syncthreads();  // the previous member's rows have been read
+    eng.global_to_lds(lds, twM, load);  // rows at out_at(b, x); ends with a barrier
+    fock_rows<false>(lds, members.a[m] + row0, acc + row0, members.w[m], yl * n, [&](int idx) {
+      const int b = idx / n;
+      return eng.out_at(b, idx - b * n);
+    });
+  }
+}
+
+// Engines whose batched accumulating x stage keeps the member loop inside the
+// workgroup; the others run one single-pair launch per member, in order on the
+// stream (the DensityBandLoop pattern). The fp32 N = 1024 compile-time engine
+// does not: with the loop its kernel took all 256 VGPRs and 96 B of scratch
+// per lane (23 spilled registers).
+template <class Eng>
+struct FockBandLoop {
+  static constexpr bool value = true;
+};
+template <int S, bool LF, bool TwPre>
+struct FockBandLoop<CtEng<float, 1024, S, LF, TwPre>> {
+  static constexpr bool value = false;
+};
 
 // The composed pair operator's two passes over the space domain (R2C transforms
 // and long x lines): E = cx<T> or T (conj is then the identity).

@@ -295,6 +295,79 @@ void launch_x_backward_fock(const XArgs& a, const cx<T>* inter, const cx<T>* pa,
   });
 }
 
+// Batched pair operator: the members over the grid's z extent in the forward x
+// and the z stage, looped over inside the workgroup in the accumulating x stage.
+// plainLoads: default-policy loads of a and b (one b shared by the batch: the
+// later members find it in the caches) instead of streaming ones.
+template <typename T>
+void launch_x_forward_pair_batch(const XArgs& a, const cx<T>* const* pb, bool plainLoads, const cx<T>* tw,
+                                 hipStream_t stream) {
+  if (a.L <= a.zBegin || a.Y <= 0 || a.batch.count < 1 || a.batch.count > kMaxBatch) return;
+  PairSecond<T> second{};
+  for (int m = 0; m < a.batch.count; ++m) second.b[m] = pb[m];
+  with_engine<T, -1, true>(a.n, [&](auto eng, int threads, int lines, std::size_t lds) {
+    using E = decltype(eng);
+    auto k = plainLoads ? x_forward_pair_batch_kernel<E, T, false> : x_forward_pair_batch_kernel<E, T, true>;
+    const std::size_t ldsTotal = lds + std::size_t(a.n) * sizeof(int) + 16;
+    prepare_kernel(k, ldsTotal);
+    hipLaunchKernelGGL(k, dim3(ceil_div(a.Y, lines), a.L - a.zBegin, static_cast<unsigned>(a.batch.count)),
+                       dim3(threads), ldsTotal, stream, eng, a, second, tw);
+    gpu_check_launch("x_forward_pair_batch", stream);
+  });
+}
+
+template <typename T>
+void launch_z_reciprocal_batch(const ZArgs& a, bool complexKernel, T scale, const cx<T>* tw, hipStream_t stream) {
+  if (a.numSticks <= a.stickBegin || a.batch.count < 1 || a.batch.count > kMaxBatch) return;
+  with_engine<T, +1>(a.n, [&](auto eng, int threads, int lines, std::size_t lds) {
+    auto fwd = forward_twin(eng);
+    using E = decltype(eng);
+    using F = decltype(fwd);
+    const bool plain = a.plainSticks != 0;
+    auto k = complexKernel
+                 ? (plain ? z_reciprocal_batch_kernel<E, F, T, true, true> : z_reciprocal_batch_kernel<E, F, T, true, false>)
+                 : (plain ? z_reciprocal_batch_kernel<E, F, T, false, true> : z_reciprocal_batch_kernel<E, F, T, false, false>);
+    std::size_t ldsTotal = 0;
+    const ZArgs b = z_args_for_lds(a, lds, lines, &ldsTotal);
+    prepare_kernel(k, ldsTotal);
+    hipLaunchKernelGGL(k, dim3(ceil_div(a.numSticks - a.stickBegin, lines), 1, static_cast<unsigned>(a.batch.count)),
+                       dim3(threads), ldsTotal, stream, eng, fwd, b, scale, tw);
+    gpu_check_launch("z_reciprocal_batch", stream);
+  });
+}
+
+template <typename T>
+void launch_x_backward_fock_batch(const XArgs& a, const cx<T>* const* pa, const T* weights, cx<T>* acc,
+                                  const cx<T>* tw, hipStream_t stream) {
+  if (a.L <= a.zBegin || a.Y <= 0 || a.batch.count < 1 || a.batch.count > kMaxBatch) return;
+  FockMembers<T> members{};
+  for (int m = 0; m < a.batch.count; ++m) {
+    members.a[m] = pa[m];
+    members.w[m] = weights[m];
+  }
+  with_engine<T, +1, true>(a.n, [&](auto eng, int threads, int lines, std::size_t lds) {
+    using E = decltype(eng);
+    const std::size_t ldsTotal = lds + std::size_t(a.n) * sizeof(int) + 16;
+    const dim3 grid(ceil_div(a.Y, lines), a.L - a.zBegin, 1);
+    if constexpr (FockBandLoop<E>::value) {
+      auto k = x_backward_fock_batch_kernel<E, T>;
+      prepare_kernel(k, ldsTotal);
+      hipLaunchKernelGGL(k, grid, dim3(threads), ldsTotal, stream, eng, a, members, acc, tw);
+      gpu_check_launch("x_backward_fock_batch", stream);
+    } else {
+      auto single = x_backward_fock_kernel<E, T, SPFFT_FOCK_STREAM != 0>;
+      prepare_kernel(single, ldsTotal);
+      XArgs one = a;
+      one.batch.count = 0;
+      for (int m = 0; m < a.batch.count; ++m) {
+        hipLaunchKernelGGL(single, grid, dim3(threads), ldsTotal, stream, eng, one,
+                           static_cast<const cx<T>*>(a.batch.in[m]), members.a[m], acc, members.w[m], tw);
+        gpu_check_launch("x_backward_fock", stream);
+      }
+    }
+  });
+}
+
 // space[i] = conj(a[i]) * b[i] over `count` elements (complex or, realSpace, real)
 template <typename T>
 void launch_space_pair(void* space, const T* pa, const T* pb, long long count, bool realSpace,

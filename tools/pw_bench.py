@@ -14,7 +14,9 @@ process, and prints the GPU stage times of both and the modelled bytes of the tw
 z stages; with --r2c on an R2C transform; --op fock times one exchange pair,
 accumulate_fock on the model's pair-density transform (the sphere |G|^2/2 <= 4
 ecut) against torch product, apply_reciprocal, torch addcmul_, with the same
-protocol and the modelled bytes of both.)
+protocol and the modelled bytes of both; with --transforms T > 1 it times T
+pairs of one band per multi_transform_accumulate_fock call against the same T
+pairs as T single accumulate_fock calls into one acc, pairs per second of both.)
 """
 import argparse
 import json
@@ -46,9 +48,13 @@ def main():
     from spfft_amd.models import PlaneWaveBasis, PlaneWaveModel
     basis = PlaneWaveBasis(alat=a.alat, ecut=a.ecut,
                            fft_dims=(a.grid,) * 3 if a.grid else None)
-    model = PlaneWaveModel(basis, processing_unit=sp.ProcessingUnit.GPU, num_transforms=a.transforms)
+    model = PlaneWaveModel(basis, processing_unit=sp.ProcessingUnit.GPU,
+                           num_transforms=1 if a.op == "fock" else a.transforms)
     if a.op == "fock":
-        fock(a, basis, model)
+        if a.transforms > 1:
+            fock_multi(a, basis, model)
+        else:
+            fock(a, basis, model)
         return
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev)
@@ -249,6 +255,103 @@ def fock(a, basis, model):
                       "gpu_stage_median_s": stages,
                       "model_bytes": model_bytes,
                       "model_ratio": model_bytes["composed"] / model_bytes["fused"]}), flush=True)
+
+
+def _scope_medians(tree, names):
+    """identifier -> median seconds of the named host scopes, wherever they sit in the tree."""
+    out = {}
+
+    def walk(nodes):
+        for n in nodes:
+            if n["identifier"] in names:
+                out[n["identifier"]] = n["median"]
+            walk(n.get("sub-timings", []))
+
+    walk(tree["timings"])
+    return out
+
+
+def fock_multi(a, basis, model):
+    """T = --transforms exchange pairs (a_i, b) of one band b into one acc: one
+    multi_transform_accumulate_fock call on the pair-density transform and its clones
+    against the same T pairs as T single accumulate_fock calls, in alternating rounds of
+    one process (medians over at least 7 rounds, per pair), then the timing tree of each
+    variant (GPU stage times of the single calls, which mark their stages; host scopes of
+    both) and the modelled bytes per pair."""
+    import torch
+
+    import spfft_amd as sp
+    nx, ny, nz = basis.fft_dims
+    T = a.transforms
+    ts = model._exchange_transforms(T)
+    t = ts[0]
+    idx = model.exchange_indices
+    k = model._exchange_setup()[3]
+    g = torch.Generator(device="cuda")
+    g.manual_seed(6)
+    shape = (nz, ny, nx)
+    pas = [torch.randn(shape, dtype=torch.complex128, device="cuda", generator=g) for _ in range(T)]
+    pb = torch.randn(shape, dtype=torch.complex128, device="cuda", generator=g)
+    acc = torch.zeros(shape, dtype=torch.complex128, device="cuda")
+    weights = [-1.0 - 0.125 * i for i in range(T)]
+
+    def call(multi):
+        if multi:
+            return sp.multi_transform_accumulate_fock(ts, pas, [pb] * T, k, weights, acc,
+                                                      scaling=sp.Scaling.FULL)
+        for pa, w in zip(pas, weights):
+            t.accumulate_fock(pa, pb, k, w, acc, scaling=sp.Scaling.FULL)
+        return acc
+    rounds, calls = max(7, a.reps), max(2, 20 // T)
+    times = {"multi": [], "single": []}
+    for multi in (True, False):
+        call(multi)
+    for _ in range(rounds):
+        for name, multi in (("multi", True), ("single", False)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                call(multi)
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / (calls * T))
+    med = {k_: sorted(v)[len(v) // 2] for k_, v in times.items()}
+    stages, scopes = {}, {}
+    for name, multi in (("multi", True), ("single", False)):
+        sp.timing_reset()
+        sp.timing_enable(True)
+        try:
+            for _ in range(calls):
+                call(multi)
+            torch.cuda.synchronize()
+            tree = sp.timing_json()
+            stages[name] = _gpu_stage_medians(tree)
+            scopes[name] = _scope_medians(tree, {"multi_accumulate_fock", "accumulate_fock",
+                                                 "gpu_accumulate_fock_batch", "gpu_fock_forward_xy",
+                                                 "gpu_reciprocal_z", "gpu_fock_backward_xy"})
+        finally:
+            sp.timing_enable(False)
+    key = idx[:, 0].astype("int64") * (2 * ny + 1) + idx[:, 1]
+    sticks = len(set(key.tolist()))
+    columns = len(set(idx[:, 0].tolist()))
+    grid_bytes = nx * ny * nz * 16
+    inter_bytes, stick_bytes = columns * ny * nz * 16, sticks * nz * 16
+    # per pair, both variants: the intermediate and the stick array written and read once
+    # per direction, K read, a read by either x stage. A single call also reads b and
+    # reads and writes acc; a batch reads b and reads and writes acc once for its T pairs
+    # (the members' revisits of a tile stay in the caches).
+    common = 4 * inter_bytes + 4 * stick_bytes + len(idx) * 8 + 2 * grid_bytes
+    model_bytes = {"single": common + 3 * grid_bytes, "multi": common + 3 * grid_bytes / T}
+    print(json.dumps({"workload": "plane-wave exchange pairs", "fft_dims": list(basis.fft_dims),
+                      "pairs_per_call": T, "num_values": len(idx), "sticks": sticks,
+                      "batch": os.environ.get("SPFFT_BATCH", "1"),
+                      "fock_fused": t.fock_fused, "reciprocal_fused": t.reciprocal_fused,
+                      "rounds": rounds, "calls_per_round": calls,
+                      "pairs_per_s": {k_: 1.0 / v for k_, v in med.items()},
+                      "min_s_per_pair": {k_: min(v) for k_, v in times.items()},
+                      "ratio_single_over_multi": med["single"] / med["multi"],
+                      "gpu_stage_median_s": stages, "host_scope_median_s": scopes,
+                      "model_bytes_per_pair": model_bytes,
+                      "model_ratio": model_bytes["single"] / model_bytes["multi"]}), flush=True)
 
 
 if __name__ == "__main__":
