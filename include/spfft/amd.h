@@ -290,6 +290,57 @@ SPFFT_EXPORT SpfftError spfft_amd_float_multi_transform_accumulate_fock(
 SPFFT_EXPORT SpfftError spfft_amd_transform_fock_fused(SpfftTransform t, int* fused);
 SPFFT_EXPORT SpfftError spfft_amd_float_transform_fock_fused(SpfftFloatTransform t, int* fused);
 
+/* Reciprocal fan-out (gradient-like): one forward transform feeds n backward
+ * transforms,
+ *   c = scale * forward_0(space_0),  space_i = backward_i(K_i * c), i = 0 .. n-1,
+ * on the space domains of n transforms on distinct grids (a transform and its
+ * clones) at location; space_0 is both the input and member 0's result. The
+ * transforms must have equal dimensions, type, local planes and local element
+ * count: values are matched by position. kernels[i] holds one entry per local
+ * value in index order, all real or all interleaved complex (kernelIsComplex);
+ * the pointers may be equal. values may be NULL; otherwise it receives c, as in
+ * spfft_amd_transform_apply_reciprocal. kernels[i] and values are host or
+ * device pointers; scaling is SPFFT_NO_SCALING or SPFFT_FULL_SCALING. Identical
+ * plans on one GPU with the fused z stage, device pointers, location
+ * SPFFT_PU_GPU, n <= 8 and z lines that fit a workgroup's LDS twice
+ * (spfft_amd_transform_reciprocal_fan_fused) run x and y forward of member 0,
+ * one z kernel that transforms each stick block once and writes n stick arrays,
+ * and one batched launch per backward stage (SPFFT_BATCH); everything else runs
+ * forward_0 and, per member in list order, a multiply of the values and
+ * backward_i. n == 1 is spfft_amd_transform_apply_reciprocal, n == 0 a no-op.
+ * Collective on distributed grids (per transform, in list order). A repeated
+ * grid, null transforms or kernels with n > 0, a null kernels[i] with local
+ * values, unequal transforms or a bad scaling is SPFFT_INVALID_PARAMETER_ERROR;
+ * the transforms stay usable after an error. */
+SPFFT_EXPORT SpfftError spfft_amd_multi_transform_reciprocal_fan_out(
+    int n, SpfftTransform* transforms, SpfftProcessingUnitType location, const double* const* kernels,
+    int kernelIsComplex, double* values, SpfftScalingType scaling);
+SPFFT_EXPORT SpfftError spfft_amd_float_multi_transform_reciprocal_fan_out(
+    int n, SpfftFloatTransform* transforms, SpfftProcessingUnitType location, const float* const* kernels,
+    int kernelIsComplex, float* values, SpfftScalingType scaling);
+/* Reciprocal fan-in (divergence-like): n forward transforms feed one backward
+ * transform,
+ *   space_0 = backward_0(sum_i K_i * (scale * forward_i(space_i))),
+ * summed in list order; the space domains of the members i > 0 are left
+ * unchanged. Arguments, fused and composed paths and errors as for
+ * spfft_amd_multi_transform_reciprocal_fan_out (the fused z kernel sums the
+ * members' coefficients per stick block in LDS; the composition runs forward_i
+ * and a multiply-add into one values buffer per member, then backward_0); there
+ * is no values output. The sum order is fixed by the call alone: the same call
+ * on the same data gives the same bits. */
+SPFFT_EXPORT SpfftError spfft_amd_multi_transform_reciprocal_fan_in(
+    int n, SpfftTransform* transforms, SpfftProcessingUnitType location, const double* const* kernels,
+    int kernelIsComplex, SpfftScalingType scaling);
+SPFFT_EXPORT SpfftError spfft_amd_float_multi_transform_reciprocal_fan_in(
+    int n, SpfftFloatTransform* transforms, SpfftProcessingUnitType location, const float* const* kernels,
+    int kernelIsComplex, SpfftScalingType scaling);
+/* *fused = 1 if t and n - 1 clones of it, called with device pointers at
+ * SPFFT_PU_GPU, run the fused z kernel of the two calls above (n == 1: that of
+ * apply_reciprocal), else 0. */
+SPFFT_EXPORT SpfftError spfft_amd_transform_reciprocal_fan_fused(SpfftTransform t, int n, int* fused);
+SPFFT_EXPORT SpfftError spfft_amd_float_transform_reciprocal_fan_fused(SpfftFloatTransform t, int n,
+                                                                       int* fused);
+
 /* Timer tree (SPFFT_TIMING=1 or spfft_amd_timing_enable). enable: 0 off, 1 host
  * scopes only (like the reference's timer), 2 host scopes and GPU stage times
  * (a hipEvent per stage boundary, nodes gpu/<direction>/<stage>). */

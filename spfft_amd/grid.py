@@ -545,6 +545,15 @@ class _TransformBase:
             c = self._cache["reciprocal_fused"] = bool(v.value)
         return c
 
+    def reciprocal_fan_fused(self, n: int) -> bool:
+        """True if this transform and n - 1 clones of it, called with device arrays, run the
+        fused z kernel of multi_transform_reciprocal_fan_out / fan_in (reciprocal_fused
+        plans on one GPU without exchange, 2 <= n <= 8, z lines that fit a workgroup's LDS
+        twice, SPFFT_BATCH not 0); n == 1 follows reciprocal_fused."""
+        v = ctypes.c_int()
+        _check(self._prec.amd_fn("transform_reciprocal_fan_fused")(self._h, int(n), ctypes.byref(v)))
+        return bool(v.value)
+
     def accumulate_fock(self, a, b, kernel, weight, acc, values=None, scaling=Scaling.NONE):
         """Exchange (Fock) pair operator in one call:
         acc += weight * a * backward(kernel * forward(conj(a) * b, scaling)).
@@ -824,3 +833,110 @@ def multi_transform_accumulate_fock(transforms, a, b, kernel, weights, acc, scal
     for t in transforms:
         t._step_keep = keeps
     return acc
+
+
+def _fan_args(transforms, kernels, what):
+    """Handles, kernel pointers and keepalives shared by the two fan operators."""
+    n, prec, arr = _multi(transforms)
+    if _is_torch(kernels) or isinstance(kernels, np.ndarray):
+        raise TypeError(f"{what}: kernels is a sequence of one array per transform")
+    kernels = list(kernels)
+    if len(kernels) != n:
+        raise ValueError(f"{what}: one kernel per transform")
+    if any(t._single != prec.single for t in transforms):
+        raise TypeError("transforms of one call share one precision")
+    kptrs = (ctypes.c_void_p * max(1, n))()
+    keeps, cplx, seen = [], None, {}
+    for i, t in enumerate(transforms):
+        first = seen.get(id(kernels[i]))
+        if first is not None and t.num_local_elements == transforms[first].num_local_elements:
+            kptrs[i], kkeep, c = kptrs[first], None, cplx  # one conversion, one pointer
+        else:
+            kptrs[i], kkeep, c = _kernel_ptr(kernels[i], prec, t.num_local_elements)
+            seen[id(kernels[i])] = i
+        if cplx is None:
+            cplx = c
+        elif c != cplx:
+            raise TypeError("kernels of one call are all real or all complex")
+        keeps.append(kkeep)
+    return n, prec, arr, kptrs, bool(cplx), keeps
+
+
+def _fill_space(t, space, location):
+    dst = t.space_domain(location)
+    if _is_torch(dst):
+        dst.copy_(space if _is_torch(space) else torch.as_tensor(np.asarray(space)))
+    else:
+        src = space.cpu().numpy() if _is_torch(space) else np.asarray(space)
+        np.copyto(dst, src.reshape(dst.shape), casting="same_kind")
+
+
+def multi_transform_reciprocal_fan_out(transforms, kernels, space=None, values=None, location=None,
+                                       scaling=Scaling.NONE):
+    """Reciprocal fan-out (gradient-like) in one call: with c = forward(f, scaling) of the
+    space domain f of transforms[0], the space domain of transforms[i] becomes
+    backward(kernels[i] * c) for every i; member 0's space domain is input and result.
+
+    The transforms live on distinct grids (a transform and its clones) and have equal
+    dimensions, type and index sets sizes; `kernels` holds one real or complex array per
+    transform as in apply_reciprocal (all real or all complex; the same array may be given
+    several times). `space` (optional) is copied into member 0's space domain first,
+    `values` (optional) receives c. `location` is where the space domains are read and
+    written (default: member 0's processing unit). Identical fused plans on one GPU (see
+    Transform.reciprocal_fan_fused) run one forward transform, one z kernel that writes
+    every member's sticks, and one batched launch per backward stage. Returns the list of
+    space-domain views at `location`."""
+    n, prec, arr, kptrs, cplx, keeps = _fan_args(transforms, kernels, "reciprocal_fan_out")
+    if n == 0:
+        _check(prec.amd_fn("multi_transform_reciprocal_fan_out")(0, arr, 1, kptrs, 0, None, int(scaling)))
+        return []
+    if location is None:
+        location = transforms[0].processing_unit
+    if values is not None:
+        t0 = transforms[0]
+        cnt = values.numel() if _is_torch(values) else np.asarray(values).size
+        dt = values.dtype if _is_torch(values) else np.asarray(values).dtype
+        if dt != (prec.torch_complex if _is_torch(values) else prec.complex):
+            raise TypeError(f"values: expected complex of the transforms' precision, got {dt}")
+        if cnt != t0.num_local_elements:
+            raise ValueError(f"values: expected {t0.num_local_elements} entries, got {cnt}")
+    vptr, vkeep = _data_ptr(values, prec, True, "values")
+    if space is not None:
+        _fill_space(transforms[0], space, location)
+    _check(prec.amd_fn("multi_transform_reciprocal_fan_out")(
+        n, arr, int(location), kptrs, 1 if cplx else 0, vptr, int(scaling)))
+    # asynchronous execution (set_stream(..., synchronous=False)) may still use them
+    for t in transforms:
+        t._step_keep = (keeps, vkeep)
+    return [t.space_domain(location) for t in transforms]
+
+
+def multi_transform_reciprocal_fan_in(transforms, kernels, spaces=None, location=None,
+                                      scaling=Scaling.NONE):
+    """Reciprocal fan-in (divergence-like) in one call: the space domain of transforms[0]
+    becomes backward(sum_i kernels[i] * forward_i(f_i, scaling)) with f_i the space domain
+    of transforms[i], summed in list order; the space domains of the other members are
+    left unchanged.
+
+    Transforms, `kernels`, `location` and the fused path are as in
+    multi_transform_reciprocal_fan_out. `spaces` (optional) holds one array per transform
+    (or None to keep a member's contents), copied into the space domains first. The sum
+    order is fixed by the call: the same call on the same data gives the same bits.
+    Returns the space-domain view of member 0 at `location`."""
+    n, prec, arr, kptrs, cplx, keeps = _fan_args(transforms, kernels, "reciprocal_fan_in")
+    if n == 0:
+        _check(prec.amd_fn("multi_transform_reciprocal_fan_in")(0, arr, 1, kptrs, 0, int(scaling)))
+        return None
+    if location is None:
+        location = transforms[0].processing_unit
+    if spaces is not None:
+        if len(spaces) != n:
+            raise ValueError("reciprocal_fan_in: one space array (or None) per transform")
+        for t, s in zip(transforms, spaces):
+            if s is not None:
+                _fill_space(t, s, location)
+    _check(prec.amd_fn("multi_transform_reciprocal_fan_in")(
+        n, arr, int(location), kptrs, 1 if cplx else 0, int(scaling)))
+    for t in transforms:
+        t._step_keep = (keeps,)
+    return transforms[0].space_domain(location)

@@ -303,6 +303,70 @@ class PlaneWaveModel:
             out.append(c.clone() if hasattr(c, "clone") else np.array(c))
         return out
 
+    def gradient_kernels(self):
+        """K_d(G) = i G_d, d = x, y, z, on the density sphere |G|^2/2 <= 4 ecut (the index
+        set of the pair-density transform): complex, in the transforms' precision, where
+        the transforms run."""
+        ks = getattr(self, "_gradient_kernels", None)
+        if ks is None:
+            t, trip, _, _ = self._exchange_setup()
+            unit = 2 * np.pi / self.basis.alat
+            ks = [(1j * unit * trip[:, d].astype(np.float64)).astype(t._prec.complex)
+                  for d in range(3)]
+            if self.pu == ProcessingUnit.GPU:
+                import torch
+                ks = [torch.as_tensor(k, device=f"cuda:{t.device_id}") for k in ks]
+            self._gradient_kernels = ks
+        return ks
+
+    @staticmethod
+    def _copy(a):
+        return a.clone() if hasattr(a, "clone") else np.array(a)
+
+    def gradient(self, f, unfused: bool = False) -> List:
+        """(d_x f, d_y f, d_z f) of a grid function f [z][y][x] on the density sphere:
+        d_d f = FFT^-1[ i G_d FFT[f](G) ], as three new complex arrays.
+
+        One multi_transform_reciprocal_fan_out call on the pair-density transform and two
+        clones (on the GPU one forward transform, one z kernel that transforms each stick
+        block once and feeds three inverse z FFTs, and one launch per backward stage for
+        the three components); `unfused` runs the composition forward, then per component
+        multiply and backward."""
+        from ..grid import multi_transform_reciprocal_fan_out
+        ts = self._exchange_transforms(3)
+        ks = self.gradient_kernels()
+        if not unfused:
+            return [self._copy(s) for s in
+                    multi_transform_reciprocal_fan_out(ts, ks, space=f, scaling=Scaling.FULL)]
+        t = ts[0]
+        c = self._copy(t.forward(space=f, scaling=Scaling.FULL))
+        return [self._copy(t.backward(c * k)) for k in ks]
+
+    def divergence(self, fields: Sequence, unfused: bool = False):
+        """div h = sum_d FFT^-1[ i G_d FFT[h_d](G) ] of a vector field (h_x, h_y, h_z) of
+        grid functions [z][y][x] on the density sphere, as a new complex array.
+
+        One multi_transform_reciprocal_fan_in call on the pair-density transform and two
+        clones (on the GPU one launch per forward stage for the three components, one z
+        kernel that sums i G_d c_d per stick block in LDS, and one backward transform);
+        `unfused` runs three forward transforms, the multiply-add of the values and one
+        backward transform."""
+        from ..grid import multi_transform_reciprocal_fan_in
+        fields = list(fields)
+        if len(fields) != 3:
+            raise ValueError("divergence: three fields (x, y, z components)")
+        ts = self._exchange_transforms(3)
+        ks = self.gradient_kernels()
+        if not unfused:
+            return self._copy(multi_transform_reciprocal_fan_in(ts, ks, spaces=fields,
+                                                                scaling=Scaling.FULL))
+        t = ts[0]
+        s = None
+        for h, k in zip(fields, ks):
+            c = t.forward(space=h, scaling=Scaling.FULL) * k
+            s = c if s is None else s + c
+        return self._copy(t.backward(s))
+
     def kinetic(self, psi: Sequence) -> List:
         """T psi_b = |G|^2/2 c_G (diagonal in the plane-wave basis)."""
         g2 = self.basis.g2

@@ -135,6 +135,10 @@ def _prototypes(lib):
         sig[pre + "transform_fock_fused"] = [V, c_int_p]
         sig[pre + "multi_transform_accumulate_fock"] = [I, c_void_pp, c_void_pp, c_void_pp,
                                                         c_void_pp, I, D, D, I]
+    for pre in ("spfft_amd_", "spfft_amd_float_"):
+        sig[pre + "multi_transform_reciprocal_fan_out"] = [I, c_void_pp, I, c_void_pp, I, D, I]
+        sig[pre + "multi_transform_reciprocal_fan_in"] = [I, c_void_pp, I, c_void_pp, I, I]
+        sig[pre + "transform_reciprocal_fan_fused"] = [V, I, c_int_p]
     sig["spfft_amd_timing_enable"] = [I]
     sig["spfft_amd_timing_reset"] = []
     sig["spfft_amd_timing_json"] = [ctypes.c_char_p, ctypes.c_size_t, c_size_t_p]

@@ -49,6 +49,18 @@ void multi_accumulate_fock_handles(int n, Transform** ts, const double* const* a
 void multi_accumulate_fock_handles(int n, TransformFloat** ts, const float* const* a, const float* const* b,
                                    const float* const* kernels, bool complexKernel, const float* weights,
                                    float* acc, SpfftScalingType scaling);
+void multi_reciprocal_fan_out_handles(int n, Transform** ts, SpfftProcessingUnitType location,
+                                      const double* const* kernels, bool complexKernel, double* values,
+                                      SpfftScalingType scaling);
+void multi_reciprocal_fan_out_handles(int n, TransformFloat** ts, SpfftProcessingUnitType location,
+                                      const float* const* kernels, bool complexKernel, float* values,
+                                      SpfftScalingType scaling);
+void multi_reciprocal_fan_in_handles(int n, Transform** ts, SpfftProcessingUnitType location,
+                                     const double* const* kernels, bool complexKernel,
+                                     SpfftScalingType scaling);
+void multi_reciprocal_fan_in_handles(int n, TransformFloat** ts, SpfftProcessingUnitType location,
+                                     const float* const* kernels, bool complexKernel,
+                                     SpfftScalingType scaling);
 }  // namespace spfft
 
 using namespace spfft;
@@ -687,6 +699,66 @@ SpfftError spfft_amd_float_transform_fock_fused(SpfftFloatTransform t, int* fuse
   if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
   return with_handle<TransformFloat>(
       t, [&](TransformFloat& x) { *fused = x.impl()->fock_fused() ? 1 : 0; });
+}
+
+SpfftError spfft_amd_multi_transform_reciprocal_fan_out(int n, SpfftTransform* transforms,
+                                                        SpfftProcessingUnitType location,
+                                                        const double* const* kernels, int kernelIsComplex,
+                                                        double* values, SpfftScalingType scaling) {
+  if (n > 0 && !transforms) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < n; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_reciprocal_fan_out_handles(n, reinterpret_cast<Transform**>(transforms), location, kernels,
+                                     kernelIsComplex != 0, values, scaling);
+  });
+}
+SpfftError spfft_amd_float_multi_transform_reciprocal_fan_out(int n, SpfftFloatTransform* transforms,
+                                                              SpfftProcessingUnitType location,
+                                                              const float* const* kernels,
+                                                              int kernelIsComplex, float* values,
+                                                              SpfftScalingType scaling) {
+  if (n > 0 && !transforms) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < n; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_reciprocal_fan_out_handles(n, reinterpret_cast<TransformFloat**>(transforms), location, kernels,
+                                     kernelIsComplex != 0, values, scaling);
+  });
+}
+SpfftError spfft_amd_multi_transform_reciprocal_fan_in(int n, SpfftTransform* transforms,
+                                                       SpfftProcessingUnitType location,
+                                                       const double* const* kernels, int kernelIsComplex,
+                                                       SpfftScalingType scaling) {
+  if (n > 0 && !transforms) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < n; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_reciprocal_fan_in_handles(n, reinterpret_cast<Transform**>(transforms), location, kernels,
+                                    kernelIsComplex != 0, scaling);
+  });
+}
+SpfftError spfft_amd_float_multi_transform_reciprocal_fan_in(int n, SpfftFloatTransform* transforms,
+                                                             SpfftProcessingUnitType location,
+                                                             const float* const* kernels,
+                                                             int kernelIsComplex, SpfftScalingType scaling) {
+  if (n > 0 && !transforms) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < n; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_reciprocal_fan_in_handles(n, reinterpret_cast<TransformFloat**>(transforms), location, kernels,
+                                    kernelIsComplex != 0, scaling);
+  });
+}
+SpfftError spfft_amd_transform_reciprocal_fan_fused(SpfftTransform t, int n, int* fused) {
+  if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
+  return with_handle<Transform>(
+      t, [&](Transform& x) { *fused = x.impl()->reciprocal_fan_fused(n) ? 1 : 0; });
+}
+SpfftError spfft_amd_float_transform_reciprocal_fan_fused(SpfftFloatTransform t, int n, int* fused) {
+  if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
+  return with_handle<TransformFloat>(
+      t, [&](TransformFloat& x) { *fused = x.impl()->reciprocal_fan_fused(n) ? 1 : 0; });
 }
 
 SpfftError spfft_amd_timing_enable(int enable) {

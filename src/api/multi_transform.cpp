@@ -361,6 +361,185 @@ void multi_accumulate_fock(const std::vector<TransformImpl<T>*>& ts, const T* co
     if (ts[i]->is_gpu() && ts[i]->gpu()->synchronous()) ts[i]->synchronize();
 }
 
+// ---------------------------------------------- reciprocal fan-out and fan-in
+// out = in * K or out += in * K over `count` interleaved complex host values
+// (the multiply of TransformImpl::reciprocal_z)
+template <typename T>
+void host_values_scale(T* out, const T* in, const T* kernel, bool complexKernel, std::size_t count, bool add) {
+  for (std::size_t i = 0; i < count; ++i) {
+    const T re = in[2 * i], im = in[2 * i + 1];
+    T pr, pi;
+    if (complexKernel) {
+      pr = re * kernel[2 * i] - im * kernel[2 * i + 1];
+      pi = re * kernel[2 * i + 1] + im * kernel[2 * i];
+    } else {
+      pr = re * kernel[i];
+      pi = im * kernel[i];
+    }
+    out[2 * i] = add ? out[2 * i] + pr : pr;
+    out[2 * i + 1] = add ? out[2 * i + 1] + pi : pi;
+  }
+}
+
+// The checks both fan operators share; returns whether the fused z stage runs:
+// GPU transforms with device space domains, reciprocal_fan_fused plans with
+// equal keys, at most dev::kMaxBatch of them, device kernels.
+template <typename T>
+bool check_fan(const std::vector<TransformImpl<T>*>& ts, SpfftProcessingUnitType location,
+               const T* const* kernels, SpfftScalingType scaling) {
+  check_distinct_grids(ts);
+  const int n = static_cast<int>(ts.size());
+  if (n > 0 && !kernels) throw InvalidParameterError();
+  if (scaling != SPFFT_NO_SCALING && scaling != SPFFT_FULL_SCALING) throw InvalidParameterError();
+  if (location != SPFFT_PU_HOST && location != SPFFT_PU_GPU) throw InvalidParameterError();
+  for (int i = 0; i < n; ++i) {
+    const IndexPlan& p = ts[i]->plan();
+    const IndexPlan& p0 = ts[0]->plan();
+    // values are matched by position, space domains by element
+    if (p.type != p0.type || p.dimX != p0.dimX || p.dimY != p0.dimY || p.dimZ != p0.dimZ ||
+        p.local_planes() != p0.local_planes() || p.numLocalElements != p0.numLocalElements)
+      throw InvalidParameterError();
+    if (!ts[i]->is_gpu() && location != SPFFT_PU_HOST) throw InvalidParameterError();
+    if (p.numLocalElements > 0 && !kernels[i]) throw InvalidParameterError();
+  }
+  if (n < 2 || n > dev::kMaxBatch || location != SPFFT_PU_GPU) return false;
+  for (int i = 0; i < n; ++i) {
+    if (!ts[i]->is_gpu()) return false;
+    ts[i]->gpu()->ensure_stream();
+    if (!ts[i]->gpu()->reciprocal_fan_fused() || ts[i]->gpu()->batch_key() != ts[0]->gpu()->batch_key())
+      return false;
+    if (ts[i]->plan().numLocalElements > 0 && !is_device_pointer(kernels[i])) return false;
+  }
+  return true;
+}
+
+// space_i = backward_i(K_i * c) for every member, c = scale * forward_0(space_0);
+// `values` (may be NULL) receives c. Fused plans run GpuExecutor::
+// reciprocal_fan_out_batch; everything else the composition per transform in
+// list order: forward_0 into a values buffer, then per member the multiply of
+// the values and backward_i (device buffers when every transform is a GPU
+// transform, host buffers otherwise).
+template <typename T>
+void multi_reciprocal_fan_out(const std::vector<TransformImpl<T>*>& ts, SpfftProcessingUnitType location,
+                              const T* const* kernels, bool complexKernel, T* values,
+                              SpfftScalingType scaling) {
+  SPFFT_TIMED_SCOPE("multi_reciprocal_fan_out");
+  bool fused = check_fan<T>(ts, location, kernels, scaling);
+  const int n = static_cast<int>(ts.size());
+  if (n == 0) return;
+  if (n == 1) {
+    ts[0]->apply_reciprocal(location, kernels[0], complexKernel, values, scaling);
+    return;
+  }
+  const std::size_t count = static_cast<std::size_t>(ts[0]->plan().numLocalElements);
+  if (values && count > 0 && !is_device_pointer(values)) fused = false;
+  if (fused) {
+    std::vector<GpuExecutor<T>*> ex;
+    std::vector<const T*> ks;
+    for (int i = 0; i < n; ++i) {
+      ex.push_back(ts[i]->gpu());
+      ks.push_back(kernels[i]);
+    }
+    GpuExecutor<T>::reciprocal_fan_out_batch(ex, ks, complexKernel, values, scaling);
+    for (int i = 0; i < n; ++i)
+      if (ts[i]->gpu()->synchronous()) ts[i]->synchronize();
+    return;
+  }
+  bool allGpu = true;
+  for (auto* t : ts) allGpu = allGpu && t->is_gpu();
+  if (allGpu) {
+    GpuExecutor<T>* g0 = ts[0]->gpu();
+    const bool hostValues = values && count > 0 && !is_device_pointer(values);
+    cx<T>* c = values && !hostValues ? reinterpret_cast<cx<T>*>(values) : g0->fan_buffer(0);
+    ts[0]->forward_xy(location);
+    ts[0]->forward_exchange(false);
+    ts[0]->forward_z(reinterpret_cast<T*>(c), scaling);
+    if (hostValues) g0->download_values(values, c);
+    ts[0]->synchronize();  // c is complete: the members' streams may read it
+    for (int i = 0; i < n; ++i) {
+      GpuExecutor<T>* g = ts[i]->gpu();
+      cx<T>* prod = g->fan_buffer(1);
+      g->values_scale(prod, c, kernels[i], complexKernel, false);
+      ts[i]->backward_z(reinterpret_cast<const T*>(prod));
+      ts[i]->backward_exchange(false);
+      ts[i]->backward_xy(location);
+    }
+    // (also in asynchronous mode: c may be member 0's work array, which its next call reuses)
+    for (int i = 0; i < n; ++i) ts[i]->synchronize();
+    return;
+  }
+  std::vector<T> c(2 * std::max<std::size_t>(count, 1)), prod(c.size());
+  ts[0]->forward(location, c.data(), scaling);
+  ts[0]->synchronize();
+  if (values) {
+    if (count > 0 && is_device_pointer(values)) throw InvalidParameterError();
+    std::copy(c.begin(), c.begin() + 2 * count, values);
+  }
+  for (int i = 0; i < n; ++i) {
+    host_values_scale<T>(prod.data(), c.data(), kernels[i], complexKernel, count, false);
+    ts[i]->backward(prod.data(), location);
+    ts[i]->synchronize();
+  }
+}
+
+// space_0 = backward_0(sum_i K_i * (scale * forward_i(space_i))), summed in list
+// order; the other members' space domains are only read. Fused plans run
+// GpuExecutor::reciprocal_fan_in_batch; everything else the composition per
+// transform in list order: forward_i and a multiply-add into one values buffer,
+// each update behind the previous one, then backward_0.
+template <typename T>
+void multi_reciprocal_fan_in(const std::vector<TransformImpl<T>*>& ts, SpfftProcessingUnitType location,
+                             const T* const* kernels, bool complexKernel, SpfftScalingType scaling) {
+  SPFFT_TIMED_SCOPE("multi_reciprocal_fan_in");
+  const bool fused = check_fan<T>(ts, location, kernels, scaling);
+  const int n = static_cast<int>(ts.size());
+  if (n == 0) return;
+  if (n == 1) {
+    ts[0]->apply_reciprocal(location, kernels[0], complexKernel, nullptr, scaling);
+    return;
+  }
+  const std::size_t count = static_cast<std::size_t>(ts[0]->plan().numLocalElements);
+  if (fused) {
+    std::vector<GpuExecutor<T>*> ex;
+    std::vector<const T*> ks;
+    for (int i = 0; i < n; ++i) {
+      ex.push_back(ts[i]->gpu());
+      ks.push_back(kernels[i]);
+    }
+    GpuExecutor<T>::reciprocal_fan_in_batch(ex, ks, complexKernel, scaling);
+    for (int i = 0; i < n; ++i)
+      if (ts[i]->gpu()->synchronous()) ts[i]->synchronize();
+    return;
+  }
+  bool allGpu = true;
+  for (auto* t : ts) allGpu = allGpu && t->is_gpu();
+  if (allGpu) {
+    cx<T>* sum = ts[0]->gpu()->fan_buffer(0);
+    for (int i = 0; i < n; ++i) {
+      GpuExecutor<T>* g = ts[i]->gpu();
+      cx<T>* c = g->fan_buffer(1);
+      ts[i]->forward_xy(location);
+      ts[i]->forward_exchange(false);
+      ts[i]->forward_z(reinterpret_cast<T*>(c), scaling);
+      g->values_scale(sum, c, kernels[i], complexKernel, i > 0);
+      ts[i]->synchronize();  // the next member's update of the sum comes behind this one
+    }
+    ts[0]->backward_z(reinterpret_cast<const T*>(sum));
+    ts[0]->backward_exchange(false);
+    ts[0]->backward_xy(location);
+    if (ts[0]->gpu()->synchronous()) ts[0]->synchronize();
+    return;
+  }
+  std::vector<T> c(2 * std::max<std::size_t>(count, 1)), sum(c.size());
+  for (int i = 0; i < n; ++i) {
+    ts[i]->forward(location, c.data(), scaling);
+    ts[i]->synchronize();
+    host_values_scale<T>(sum.data(), c.data(), kernels[i], complexKernel, count, i > 0);
+  }
+  ts[0]->backward(sum.data(), location);
+  ts[0]->synchronize();
+}
+
 template <typename TR, typename T>
 std::vector<TransformImpl<T>*> impls(int n, TR* transforms) {
   if (n < 0 || (n > 0 && !transforms)) throw InvalidParameterError();
@@ -454,6 +633,38 @@ void multi_accumulate_fock_handles(int n, TransformFloat** ts, const float* cons
   std::vector<TransformImpl<float>*> v;
   for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
   multi_accumulate_fock<float>(v, a, b, kernels, complexKernel, weights, acc, scaling);
+}
+void multi_reciprocal_fan_out_handles(int n, Transform** ts, SpfftProcessingUnitType location,
+                                      const double* const* kernels, bool complexKernel, double* values,
+                                      SpfftScalingType scaling) {
+  if (n < 0 || (n > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<double>*> v;
+  for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_reciprocal_fan_out<double>(v, location, kernels, complexKernel, values, scaling);
+}
+void multi_reciprocal_fan_out_handles(int n, TransformFloat** ts, SpfftProcessingUnitType location,
+                                      const float* const* kernels, bool complexKernel, float* values,
+                                      SpfftScalingType scaling) {
+  if (n < 0 || (n > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<float>*> v;
+  for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_reciprocal_fan_out<float>(v, location, kernels, complexKernel, values, scaling);
+}
+void multi_reciprocal_fan_in_handles(int n, Transform** ts, SpfftProcessingUnitType location,
+                                     const double* const* kernels, bool complexKernel,
+                                     SpfftScalingType scaling) {
+  if (n < 0 || (n > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<double>*> v;
+  for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_reciprocal_fan_in<double>(v, location, kernels, complexKernel, scaling);
+}
+void multi_reciprocal_fan_in_handles(int n, TransformFloat** ts, SpfftProcessingUnitType location,
+                                     const float* const* kernels, bool complexKernel,
+                                     SpfftScalingType scaling) {
+  if (n < 0 || (n > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<float>*> v;
+  for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_reciprocal_fan_in<float>(v, location, kernels, complexKernel, scaling);
 }
 void multi_forward_handles(int n, TransformFloat** ts, SpfftProcessingUnitType* in, float** out,
                            SpfftScalingType* sc) {

@@ -331,6 +331,12 @@ void TransformImpl<T>::backward_xy(SpfftProcessingUnitType outputLocation) {
 }
 
 template <typename T>
+bool TransformImpl<T>::reciprocal_fan_fused(int n) const {
+  if (!gpu_ || n < 1 || n > dev::kMaxBatch) return false;
+  return n == 1 ? gpu_->reciprocal_fused() : gpu_->reciprocal_fan_fused();
+}
+
+template <typename T>
 void TransformImpl<T>::synchronize() {
   if (gpu_) gpu_->synchronize();
 }

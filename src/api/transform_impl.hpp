@@ -50,6 +50,10 @@ public:
   void apply_reciprocal(SpfftProcessingUnitType location, const T* kernel, bool complexKernel,
                         T* values, SpfftScalingType scaling);
   bool reciprocal_fused() const { return gpu_ && gpu_->reciprocal_fused(); }
+  // whether this transform and n - 1 clones of it, called with device pointers,
+  // run the fused z stage of multi_transform_reciprocal_fan_out / fan_in (n == 1:
+  // that of apply_reciprocal)
+  bool reciprocal_fan_fused(int n) const;
 
   // Exchange (Fock) pair operator: acc += weight * a * backward(K * (scale *
   // forward(conj(a) * b))) with a, b and acc over the local space domain

@@ -1984,6 +1984,165 @@ void GpuExecutor<T>::accumulate_fock_batch(const std::vector<GpuExecutor*>& ex, 
   batch_release(ex);
 }
 
+// ------------------------------------------------ reciprocal fan-out and fan-in
+template <typename T>
+bool GpuExecutor<T>::reciprocal_fan_fused() const {
+  if (!batchable() || !reciprocalFused_) return false;
+  if (fanFits_ < 0) fanFits_ = dev::z_reciprocal_fan_fits<T>(zargs()) ? 1 : 0;
+  return fanFits_ == 1;
+}
+
+// One forward transform of member 0 up to the z stage, the fan-out z stage,
+// then one launch per backward stage for all members.
+template <typename T>
+void GpuExecutor<T>::reciprocal_fan_out_batch(const std::vector<GpuExecutor*>& ex,
+                                              const std::vector<const T*>& kernels, bool complexKernel,
+                                              T* values, SpfftScalingType scaling) {
+  SPFFT_TIMED_SCOPE("gpu_reciprocal_fan_out_batch");
+  const int n = static_cast<int>(ex.size());
+  if (n < 1 || n > dev::kMaxBatch || kernels.size() != ex.size()) throw InternalError();
+  GpuExecutor* l = ex[0];
+  DeviceGuard guard(l->deviceId_);
+  for (GpuExecutor* e : ex)
+    if (!e->reciprocal_fan_fused() || e->batchKey_ != l->batchKey_) throw InternalError();
+  const IndexPlan& p = *l->plan_;
+  if (p.numLocalElements > 0 && values && !is_device_pointer(values)) throw InvalidParameterError();
+  const T factor = scaling == SPFFT_FULL_SCALING
+                       ? static_cast<T>(1.0 / (static_cast<double>(p.dimX) * p.dimY * p.dimZ))
+                       : T(1);
+  dev::BatchPtrs zr{}, yb{}, xb{};
+  zr.count = yb.count = xb.count = n;
+  for (int i = 0; i < n; ++i) {
+    GpuExecutor* e = ex[i];
+    if (p.numLocalElements > 0 && (!kernels[i] || !is_device_pointer(kernels[i])))
+      throw InvalidParameterError();
+    zr.in[i] = kernels[i];
+    zr.out[i] = e->grid_->device_slot(GridImpl<T>::kStickSide);
+    yb.in[i] = e->grid_->device_slot(GridImpl<T>::kSlabSide);
+    yb.out[i] = e->grid_->device_slot(GridImpl<T>::kInter);
+    xb.in[i] = yb.out[i];
+    xb.out[i] = e->grid_->device_slot(GridImpl<T>::kSpace);
+  }
+  batch_join(ex);
+  auto za = l->zargs();
+  auto ya = l->yargs();
+  auto xa = l->xargs();
+  hipStream_t s = l->stream_;
+  const bool r2c = p.type == SPFFT_TRANS_R2C;
+  const cx<T>* twXh = l->twXh_ ? l->twXh_->data<cx<T>>() : nullptr;
+  // member 0 alone: x forward, y forward (unbatched launches)
+  dev::launch_x_forward<T>(xa, r2c, xb.out[0], static_cast<cx<T>*>(yb.out[0]), l->twX_->data<cx<T>>(), twXh, s);
+  dev::launch_y_forward<T, cx<T>>(ya, static_cast<const cx<T>*>(yb.out[0]),
+                                  static_cast<cx<T>*>(l->grid_->device_slot(GridImpl<T>::kSlabSide)),
+                                  l->twY_->data<cx<T>>(), s);
+  za.batch = zr;
+  za.plainSticks = l->plainHandoff_;
+  dev::launch_z_reciprocal_fan_out<T>(za, complexKernel, reinterpret_cast<cx<T>*>(values), factor,
+                                      l->twZ_->data<cx<T>>(), s);
+  ya.batch = yb;
+  ya.plainSticks = l->plainHandoff_;
+  dev::launch_y_backward<T, cx<T>>(ya, static_cast<const cx<T>*>(yb.in[0]), static_cast<cx<T>*>(yb.out[0]),
+                                   l->twY_->data<cx<T>>(), s);
+  xa.batch = xb;
+  dev::launch_x_backward<T>(xa, r2c, static_cast<const cx<T>*>(xb.in[0]), xb.out[0], l->twX_->data<cx<T>>(), twXh,
+                            s);
+  batch_release(ex);
+}
+
+// One launch per forward stage for all members, the fan-in z stage, then the
+// backward y and x stages of member 0 alone.
+template <typename T>
+void GpuExecutor<T>::reciprocal_fan_in_batch(const std::vector<GpuExecutor*>& ex,
+                                             const std::vector<const T*>& kernels, bool complexKernel,
+                                             SpfftScalingType scaling) {
+  SPFFT_TIMED_SCOPE("gpu_reciprocal_fan_in_batch");
+  const int n = static_cast<int>(ex.size());
+  if (n < 1 || n > dev::kMaxBatch || kernels.size() != ex.size()) throw InternalError();
+  GpuExecutor* l = ex[0];
+  DeviceGuard guard(l->deviceId_);
+  for (GpuExecutor* e : ex)
+    if (!e->reciprocal_fan_fused() || e->batchKey_ != l->batchKey_) throw InternalError();
+  const IndexPlan& p = *l->plan_;
+  const T factor = scaling == SPFFT_FULL_SCALING
+                       ? static_cast<T>(1.0 / (static_cast<double>(p.dimX) * p.dimY * p.dimZ))
+                       : T(1);
+  dev::BatchPtrs xf{}, yf{}, zr{};
+  xf.count = yf.count = zr.count = n;
+  for (int i = 0; i < n; ++i) {
+    GpuExecutor* e = ex[i];
+    if (p.numLocalElements > 0 && (!kernels[i] || !is_device_pointer(kernels[i])))
+      throw InvalidParameterError();
+    xf.in[i] = e->grid_->device_slot(GridImpl<T>::kSpace);
+    xf.out[i] = e->grid_->device_slot(GridImpl<T>::kInter);
+    yf.in[i] = xf.out[i];
+    yf.out[i] = e->grid_->device_slot(GridImpl<T>::kSlabSide);
+    zr.in[i] = kernels[i];
+    zr.out[i] = e->grid_->device_slot(GridImpl<T>::kStickSide);
+  }
+  batch_join(ex);
+  auto za = l->zargs();
+  auto ya = l->yargs();
+  auto xa = l->xargs();
+  hipStream_t s = l->stream_;
+  const bool r2c = p.type == SPFFT_TRANS_R2C;
+  const cx<T>* twXh = l->twXh_ ? l->twXh_->data<cx<T>>() : nullptr;
+  xa.batch = xf;
+  dev::launch_x_forward<T>(xa, r2c, xf.in[0], static_cast<cx<T>*>(xf.out[0]), l->twX_->data<cx<T>>(), twXh, s);
+  ya.batch = yf;
+  dev::launch_y_forward<T, cx<T>>(ya, static_cast<const cx<T>*>(yf.in[0]), static_cast<cx<T>*>(yf.out[0]),
+                                  l->twY_->data<cx<T>>(), s);
+  za.batch = zr;
+  za.plainSticks = l->plainHandoff_;
+  dev::launch_z_reciprocal_fan_in<T>(za, complexKernel, factor, l->twZ_->data<cx<T>>(), s);
+  // member 0 alone: y backward, x backward (unbatched launches)
+  auto yb = l->yargs();
+  yb.plainSticks = l->plainHandoff_;
+  dev::launch_y_backward<T, cx<T>>(yb, static_cast<const cx<T>*>(yf.out[0]), static_cast<cx<T>*>(xf.out[0]),
+                                   l->twY_->data<cx<T>>(), s);
+  auto xb = l->xargs();
+  dev::launch_x_backward<T>(xb, r2c, static_cast<const cx<T>*>(xf.out[0]),
+                            l->grid_->device_slot(GridImpl<T>::kSpace), l->twX_->data<cx<T>>(), twXh, s);
+  batch_release(ex);
+}
+
+template <typename T>
+cx<T>* GpuExecutor<T>::fan_buffer(int which) {
+  DeviceGuard guard(deviceId_);
+  const std::size_t bytes = std::max<std::size_t>(1, static_cast<std::size_t>(plan_->numLocalElements)) * sizeof(cx<T>);
+  std::unique_ptr<DeviceBuffer>& b = fanBuf_[which ? 1 : 0];
+  if (!b || b->bytes() < bytes) b.reset(new DeviceBuffer(bytes));
+  return b->data<cx<T>>();
+}
+
+template <typename T>
+void GpuExecutor<T>::values_scale(cx<T>* out, const cx<T>* in, const T* kernel, bool complexKernel, bool add) {
+  DeviceGuard guard(deviceId_);
+  const std::size_t count = static_cast<std::size_t>(plan_->numLocalElements);
+  if (count == 0) return;
+  if (!kernel) throw InvalidParameterError();
+  order_after_default_stream();
+  const T* kern = kernel;
+  if (!is_device_pointer(kernel)) {
+    const std::size_t bytes = count * (complexKernel ? sizeof(cx<T>) : sizeof(T));
+    if (!recKernel_ || recKernel_->bytes() < bytes) recKernel_.reset(new DeviceBuffer(bytes));
+    gpu_check(hipMemcpyAsync(recKernel_->data<T>(), kernel, bytes, hipMemcpyHostToDevice, stream_),
+              "hipMemcpyAsync");
+    kern = recKernel_->data<T>();
+  }
+  if (add)
+    dev::launch_values_scale_add<T>(out, in, kern, complexKernel, static_cast<long long>(count), stream_);
+  else
+    dev::launch_values_scale<T>(out, in, kern, complexKernel, static_cast<long long>(count), stream_);
+}
+
+template <typename T>
+void GpuExecutor<T>::download_values(T* hostDst, const cx<T>* src) {
+  DeviceGuard guard(deviceId_);
+  const std::size_t count = static_cast<std::size_t>(plan_->numLocalElements);
+  if (count == 0) return;
+  gpu_check(hipMemcpyAsync(hostDst, src, sizeof(cx<T>) * count, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync");
+}
+
 template class GpuExecutor<double>;
 template class GpuExecutor<float>;
 

@@ -128,6 +128,28 @@ public:
                                     bool complexKernel, const std::vector<T>& weights, T* acc,
                                     SpfftScalingType scaling, GpuExecutor* after = nullptr);
 
+  // Reciprocal fan-out and fan-in (multi_transform_reciprocal_fan_out / fan_in)
+  // of batchable() plans with a fused z stage, equal keys and a z line region
+  // that fits a workgroup's LDS twice (reciprocal_fan_fused), on the leader's
+  // stream; kernels (and values) are device pointers, the space domains are the
+  // device ones. Fan-out: x and y forward of member 0, the fan-out z stage (one
+  // forward z FFT, per member K_m multiply and inverse z FFT into its stick
+  // side), one batched y backward and one batched x backward. Fan-in: batched x
+  // and y forward, the fan-in z stage (the members' K_m-weighted coefficients
+  // summed in member order in LDS, one inverse z FFT), y and x backward of
+  // member 0; the members' space domains are only read.
+  bool reciprocal_fan_fused() const;
+  static void reciprocal_fan_out_batch(const std::vector<GpuExecutor*>& ex, const std::vector<const T*>& kernels,
+                                       bool complexKernel, T* values, SpfftScalingType scaling);
+  static void reciprocal_fan_in_batch(const std::vector<GpuExecutor*>& ex, const std::vector<const T*>& kernels,
+                                      bool complexKernel, SpfftScalingType scaling);
+  // Pieces of the composed fan paths, on this executor's stream: two device
+  // work arrays of numLocalElements values, out = in * K or out += in * K over
+  // the values (K a host or device pointer), and a copy of values to the host.
+  cx<T>* fan_buffer(int which);
+  void values_scale(cx<T>* out, const cx<T>* in, const T* kernel, bool complexKernel, bool add);
+  void download_values(T* hostDst, const cx<T>* src);
+
   void synchronize();
   bool synchronous() const { return synchronous_; }
   // Execute on `stream` (nullptr = the legacy default stream); work is then
@@ -169,6 +191,8 @@ private:
   std::unique_ptr<GpuEvent> densityEvent_;
   bool reciprocalFused_ = false;
   std::unique_ptr<DeviceBuffer> recKernel_;  // stages a host kernel
+  mutable int fanFits_ = -1;  // z line region fits the LDS twice (-1: not yet asked)
+  std::unique_ptr<DeviceBuffer> fanBuf_[2];
   bool fockFused_ = false;
   std::unique_ptr<DeviceBuffer> fockA_, fockB_, fockAcc_;  // stage host a, b, acc
   std::size_t space_elements() const;  // elements of the local space domain

@@ -202,6 +202,28 @@ void launch_z_reciprocal_batch(const ZArgs& a, bool complexKernel, T scale, cons
 template <typename T>
 void launch_x_backward_fock_batch(const XArgs& a, const cx<T>* const* pa, const T* weights, cx<T>* acc,
                                   const cx<T>* tw, hipStream_t stream);
+// Reciprocal fan-out and fan-in z stages (multi_transform_reciprocal_fan_out /
+// fan_in, simple sticks, batch.count members with identical plans; member m's
+// stick array is ZArgs::batch.out[m], its kernel K batch.in[m]). One workgroup
+// per stick block loops over the members (the grid of launch_z_reciprocal).
+// Fan-out: c = scale * forward z FFT of member 0's sticks (stored to `values`
+// when non-null), then per member the inverse z FFT of K_m * c into its stick
+// array, member 0 (in place) last. Fan-in: the sum over the members, in order,
+// of K_m * scale * forward z FFT of their sticks, one inverse z FFT into member
+// 0's stick array. Both keep the coefficients (their sum) in a second LDS
+// region; z_reciprocal_fan_fits tells whether the launch fits the LDS of a
+// workgroup (the launchers throw otherwise).
+template <typename T>
+bool z_reciprocal_fan_fits(const ZArgs& a);
+template <typename T>
+void launch_z_reciprocal_fan_out(const ZArgs& a, bool complexKernel, cx<T>* values, T scale, const cx<T>* tw,
+                                 hipStream_t stream);
+template <typename T>
+void launch_z_reciprocal_fan_in(const ZArgs& a, bool complexKernel, T scale, const cx<T>* tw, hipStream_t stream);
+// acc[i] += in[i] * kernel[i] over sparse values (composed fan-in path).
+template <typename T>
+void launch_values_scale_add(cx<T>* acc, const cx<T>* in, const T* kernel, bool complexKernel, long long count,
+                             hipStream_t stream);
 // Composed path, one pass each: space[i] = conj(a[i]) * b[i] and acc[i] +=
 // weight * a[i] * space[i] (interleaved complex or, realSpace, real arrays).
 template <typename T>

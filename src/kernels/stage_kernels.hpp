@@ -1594,6 +1594,217 @@ __global__ void __launch_bounds__(Eng::kBlock)
   });
 }
 
+// Reciprocal fan-out z stage (multi_transform_reciprocal_fan_out, simple
+// sticks): one forward z FFT of member 0's sticks feeds an inverse z FFT per
+// member. c = scale * coefficient is parked on the sparse set (zero elsewhere)
+// in a second LDS region `hold` behind the launch's other LDS (byte offset
+// holdOffset), element (b, z) at hold[b * n + z]; `values` receives c when
+// given. Per member m the line region gets K_m * c, the (0,0) stick is filled
+// and the inverse FFT stores to the member's stick array (ZArgs::batch.out[m],
+// kernel ZArgs::batch.in[m]). One workgroup owns a block of sticks and loops
+// over the members; the grid is that of z_reciprocal_kernel.
+//
+// Member 0 is written in place over the input, so it runs last; the only loads
+// of stick array 0 are those of the forward FFT, barriers before any store.
+// LDS: lane idx of the walk owns hold[idx] and the line slot of its element in
+// every loop (as in z_reciprocal_kernel), and barriers separate the walks from
+// the FFTs. Consecutive lanes touch consecutive 16- or 8-byte elements of
+// `hold`: conflict free.
+template <class Eng, class Fwd, typename T, bool Cplx, bool Plain>
+__global__ void __launch_bounds__(Eng::kBlock)
+    z_reciprocal_fan_out_kernel(Eng eng, Fwd fwd, ZArgs a, cx<T>* __restrict__ values, T scale, int holdOffset,
+                                const cx<T>* __restrict__ tw) {
+  SPFFT_LDS_DECL(T);
+  cx<T>* hold = reinterpret_cast<cx<T>*>(spfftSmem + holdOffset);
+  const int members = pin_uniform(a.batch.count);
+  const int B = eng.lines();
+  const int n = eng.n();
+  const int s0 = a.stickBegin + block_tile_x() * B;
+  const int nl = min(B, a.numSticks - s0);
+  const ZSeg seg(a.single, a.stickStride, a.zTab,
+                 reinterpret_cast<char*>(lds) + zseg_lds_offset(eng.lds_bytes(), B), n);
+  StickDesc* d = reinterpret_cast<StickDesc*>(reinterpret_cast<char*>(lds) + eng.lds_bytes());
+  for (int b = threadIdx.x; b < nl; b += blockDim.x) d[b] = a.desc[s0 + b];
+  {
+    const cx<T>* __restrict__ src = static_cast<const cx<T>*>(a.batch.out[0]);
+    // result at fwd.out_at(b, z); ends with a barrier (which also publishes d)
+    fwd.global_to_lds(lds, tw, [&](int b, int pos) -> cx<T> {
+      if (b >= nl) return czero<T>();
+      return ld_stream(&src[seg.at(s0 + b, pos)]);
+    });
+  }
+  const bool keep = pin_uniform(values != nullptr ? 1 : 0) != 0;
+  const int total = B * n;
+  for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+    const int b = idx / n, z = idx - b * n;
+    cx<T> c = czero<T>();
+    if (b < nl) {
+      const StickDesc& q = d[b];
+      const int j = desc_offset(q, z);
+      if (j >= 0) {
+        c = spfft::scale(lds[fwd.out_at(b, z)], scale);
+        if (keep) st_values(&values[q.valueStart + j], c);
+      }
+    }
+    hold[idx] = c;
+  }
+  __syncthreads();
+  for (int step = 1; step <= members; ++step) {
+    const int m = step == members ? 0 : step;
+    cx<T>* sticks = static_cast<cx<T>*>(a.batch.out[m]);
+    const T* __restrict__ kern = static_cast<const T*>(a.batch.in[m]);
+    // opaque per member: twiddle loads and the lanes' stick offsets, hoisted out
+    // of the member loop, stay live across it and cost registers
+    const cx<T>* twm = tw;
+    int s0m = s0;
+    asm volatile("" : "+s"(twm), "+s"(s0m));
+    for (int base = threadIdx.x; base < total; base += blockDim.x * kApplyUnroll) {
+      cx<T> w[kApplyUnroll];
+      int vi[kApplyUnroll];
+#pragma unroll
+      for (int u = 0; u < kApplyUnroll; ++u) {
+        const int idx = base + u * static_cast<int>(blockDim.x);
+        vi[u] = -1;
+        if (idx < total) {
+          const int b = idx / n, z = idx - b * n;
+          if (b < nl) {
+            const StickDesc& q = d[b];
+            const int j = desc_offset(q, z);
+            if (j >= 0) {
+              vi[u] = q.valueStart + j;
+              w[u] = ld_kernel<T, Cplx>(kern, vi[u]);
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kApplyUnroll; ++u) {
+        const int idx = base + u * static_cast<int>(blockDim.x);
+        if (idx < total) {
+          const int b = idx / n, z = idx - b * n;
+          cx<T> r = czero<T>();
+          if (vi[u] >= 0) {
+            const cx<T> v = hold[idx];
+            if constexpr (Cplx) r = cmul(v, w[u]);
+            else r = spfft::scale(v, w[u].x);
+          }
+          lds[eng.in_at(b, z)] = r;
+        }
+      }
+    }
+    __syncthreads();
+    if (a.zeroStick >= s0 && a.zeroStick < s0 + nl) hermitian_lines_inline(eng, lds, a.zeroStick - s0, 1, n);
+    eng.lds_to_global(lds, twm, [&](int b, int pos, cx<T> v) {
+      if (b < nl) st_stick<Plain>(&sticks[seg.at(s0m + b, pos)], v);
+    });
+    __syncthreads();  // the inverse FFT has read its lines before the next member's fill
+  }
+}
+
+// Reciprocal fan-in z stage (multi_transform_reciprocal_fan_in): per member m in
+// list order the forward z FFT of the block's sticks of ZArgs::batch.out[m],
+// then acc += K_m * (scale * coefficient) on the sparse set (K_m =
+// ZArgs::batch.in[m]); the sum's (0,0) stick is filled and one inverse z FFT
+// stores to batch.out[0]. `acc` is the second LDS region of the fan-out kernel
+// (same layout, same lane ownership: no atomics, no race, and a sum order fixed
+// by the member order alone). The stick arrays of the members m > 0 are only
+// read; member 0's is written after the last load of it (barriers in between).
+template <class Eng, class Fwd, typename T, bool Cplx, bool Plain>
+__global__ void __launch_bounds__(Eng::kBlock)
+    z_reciprocal_fan_in_kernel(Eng eng, Fwd fwd, ZArgs a, T scale, int holdOffset, const cx<T>* __restrict__ tw) {
+  SPFFT_LDS_DECL(T);
+  cx<T>* acc = reinterpret_cast<cx<T>*>(spfftSmem + holdOffset);
+  const int members = pin_uniform(a.batch.count);
+  const int B = eng.lines();
+  const int n = eng.n();
+  const int s0 = a.stickBegin + block_tile_x() * B;
+  const int nl = min(B, a.numSticks - s0);
+  const ZSeg seg(a.single, a.stickStride, a.zTab,
+                 reinterpret_cast<char*>(lds) + zseg_lds_offset(eng.lds_bytes(), B), n);
+  StickDesc* d = reinterpret_cast<StickDesc*>(reinterpret_cast<char*>(lds) + eng.lds_bytes());
+  for (int b = threadIdx.x; b < nl; b += blockDim.x) d[b] = a.desc[s0 + b];
+  const int total = B * n;
+  for (int m = 0; m < members; ++m) {
+    const cx<T>* __restrict__ src = static_cast<const cx<T>*>(a.batch.out[m]);
+    const T* __restrict__ kern = static_cast<const T*>(a.batch.in[m]);
+    // the previous member's walk has read its coefficients before these lines are reused
+    if (m > 0) __syncthreads();
+    // opaque per member: twiddle loads and the lanes' stick offsets, hoisted out
+    // of the member loop, stay live across it and cost registers
+    const cx<T>* twm = tw;
+    int s0m = s0;
+    asm volatile("" : "+s"(twm), "+s"(s0m));
+    // result at fwd.out_at(b, z); ends with a barrier (which also publishes d)
+    fwd.global_to_lds(lds, twm, [&](int b, int pos) -> cx<T> {
+      if (b >= nl) return czero<T>();
+      return ld_stream(&src[seg.at(s0m + b, pos)]);
+    });
+    for (int base = threadIdx.x; base < total; base += blockDim.x * kApplyUnroll) {
+      cx<T> w[kApplyUnroll];
+      int vi[kApplyUnroll];
+#pragma unroll
+      for (int u = 0; u < kApplyUnroll; ++u) {
+        const int idx = base + u * static_cast<int>(blockDim.x);
+        vi[u] = -1;
+        if (idx < total) {
+          const int b = idx / n, z = idx - b * n;
+          if (b < nl) {
+            const StickDesc& q = d[b];
+            const int j = desc_offset(q, z);
+            if (j >= 0) {
+              vi[u] = q.valueStart + j;
+              w[u] = ld_kernel<T, Cplx>(kern, vi[u]);
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kApplyUnroll; ++u) {
+        const int idx = base + u * static_cast<int>(blockDim.x);
+        if (idx < total) {
+          const int b = idx / n, z = idx - b * n;
+          cx<T> r = czero<T>();
+          if (vi[u] >= 0) {
+            const cx<T> v = spfft::scale(lds[fwd.out_at(b, z)], scale);
+            if constexpr (Cplx) r = cmul(v, w[u]);
+            else r = spfft::scale(v, w[u].x);
+          }
+          if (m > 0) {
+            const cx<T> s = acc[idx];
+            r = mk<T>(s.x + r.x, s.y + r.y);
+          }
+          acc[idx] = r;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+    const int b = idx / n, z = idx - b * n;
+    lds[eng.in_at(b, z)] = acc[idx];
+  }
+  __syncthreads();
+  if (a.zeroStick >= s0 && a.zeroStick < s0 + nl) hermitian_lines_inline(eng, lds, a.zeroStick - s0, 1, n);
+  cx<T>* sticks = static_cast<cx<T>*>(a.batch.out[0]);
+  eng.lds_to_global(lds, tw, [&](int b, int pos, cx<T> v) {
+    if (b < nl) st_stick<Plain>(&sticks[seg.at(s0 + b, pos)], v);
+  });
+}
+
+// acc[i] += in[i] * K[i] over `count` sparse values (the composed fan-in path).
+template <typename T, bool Cplx>
+__global__ void __launch_bounds__(256)
+    values_scale_add_kernel(cx<T>* acc, const cx<T>* __restrict__ in, const T* __restrict__ kern, long long count) {
+  const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
+  for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride) {
+    const cx<T> w = ld_kernel<T, Cplx>(kern, i);
+    cx<T> r;
+    if constexpr (Cplx) r = cmul(in[i], w);
+    else r = spfft::scale(in[i], w.x);
+    acc[i] = mk<T>(acc[i].x + r.x, acc[i].y + r.y);
+  }
+}
+
 // out[i] = in[i] * K[i] over `count` sparse values (the composed reciprocal-space
 // operator path; out may be in); K real or complex.
 template <typename T, bool Cplx>

@@ -400,5 +400,96 @@ void launch_space_fock(const void* space, const T* pa, T* acc, T weight, long lo
   gpu_check_launch("space_fock", stream);
 }
 
+// Reciprocal fan-out / fan-in z stages: the launch of launch_z_reciprocal (LDS
+// and grid of the backward z stage) plus the second LDS region that holds the
+// coefficients (fan-out) or their sum (fan-in), lines * n elements behind the
+// launch's other LDS. The workgroups loop over the batch.count members.
+constexpr std::size_t kFanLdsLimit = 160 * 1024;
+// byte offset of the hold region and the launch's LDS bytes
+inline std::size_t fan_hold_offset(std::size_t ldsTotal) { return (ldsTotal + 15) / 16 * 16; }
+template <typename T>
+inline std::size_t fan_lds_bytes(std::size_t ldsTotal, int lines, int n) {
+  return fan_hold_offset(ldsTotal) + static_cast<std::size_t>(lines) * n * sizeof(cx<T>);
+}
+
+template <typename T>
+bool z_reciprocal_fan_fits(const ZArgs& a) {
+  std::size_t fft = 0;
+  int lines = 0;
+  if (has_ct_kernel(a.n)) {
+    with_engine<T, +1>(a.n, [&](auto, int, int l, std::size_t lds) {
+      lines = l;
+      fft = lds;
+    });
+  } else {
+    fft = in_lds_engine_bytes(a.n, sizeof(cx<T>), lines);
+  }
+  std::size_t ldsTotal = 0;
+  z_args_for_lds(a, fft, lines, &ldsTotal);
+  return fan_lds_bytes<T>(ldsTotal, lines, a.n) <= kFanLdsLimit;
+}
+
+template <typename T>
+void launch_z_reciprocal_fan_out(const ZArgs& a, bool complexKernel, cx<T>* values, T scale, const cx<T>* tw,
+                                 hipStream_t stream) {
+  if (a.numSticks <= a.stickBegin || a.batch.count < 1 || a.batch.count > kMaxBatch) return;
+  with_engine<T, +1>(a.n, [&](auto eng, int threads, int lines, std::size_t lds) {
+    auto fwd = forward_twin(eng);
+    using E = decltype(eng);
+    using F = decltype(fwd);
+    const bool plain = a.plainSticks != 0;
+    auto k = complexKernel ? (plain ? z_reciprocal_fan_out_kernel<E, F, T, true, true>
+                                    : z_reciprocal_fan_out_kernel<E, F, T, true, false>)
+                           : (plain ? z_reciprocal_fan_out_kernel<E, F, T, false, true>
+                                    : z_reciprocal_fan_out_kernel<E, F, T, false, false>);
+    std::size_t ldsTotal = 0;
+    const ZArgs b = z_args_for_lds(a, lds, lines, &ldsTotal);
+    const std::size_t bytes = fan_lds_bytes<T>(ldsTotal, lines, a.n);
+    if (bytes > kFanLdsLimit) throw InternalError();
+    prepare_kernel(k, bytes);
+    hipLaunchKernelGGL(k, dim3(ceil_div(a.numSticks - a.stickBegin, lines)), dim3(threads), bytes, stream, eng, fwd,
+                       b, values, scale, static_cast<int>(fan_hold_offset(ldsTotal)), tw);
+    gpu_check_launch("z_reciprocal_fan_out", stream);
+  });
+}
+
+template <typename T>
+void launch_z_reciprocal_fan_in(const ZArgs& a, bool complexKernel, T scale, const cx<T>* tw, hipStream_t stream) {
+  if (a.numSticks <= a.stickBegin || a.batch.count < 1 || a.batch.count > kMaxBatch) return;
+  with_engine<T, +1>(a.n, [&](auto eng, int threads, int lines, std::size_t lds) {
+    auto fwd = forward_twin(eng);
+    using E = decltype(eng);
+    using F = decltype(fwd);
+    const bool plain = a.plainSticks != 0;
+    auto k = complexKernel ? (plain ? z_reciprocal_fan_in_kernel<E, F, T, true, true>
+                                    : z_reciprocal_fan_in_kernel<E, F, T, true, false>)
+                           : (plain ? z_reciprocal_fan_in_kernel<E, F, T, false, true>
+                                    : z_reciprocal_fan_in_kernel<E, F, T, false, false>);
+    std::size_t ldsTotal = 0;
+    const ZArgs b = z_args_for_lds(a, lds, lines, &ldsTotal);
+    const std::size_t bytes = fan_lds_bytes<T>(ldsTotal, lines, a.n);
+    if (bytes > kFanLdsLimit) throw InternalError();
+    prepare_kernel(k, bytes);
+    hipLaunchKernelGGL(k, dim3(ceil_div(a.numSticks - a.stickBegin, lines)), dim3(threads), bytes, stream, eng, fwd,
+                       b, scale, static_cast<int>(fan_hold_offset(ldsTotal)), tw);
+    gpu_check_launch("z_reciprocal_fan_in", stream);
+  });
+}
+
+// acc[i] += in[i] * kernel[i] over `count` sparse values (composed fan-in path)
+template <typename T>
+void launch_values_scale_add(cx<T>* acc, const cx<T>* in, const T* kernel, bool complexKernel, long long count,
+                             hipStream_t stream) {
+  if (count <= 0) return;
+  const unsigned blocks = static_cast<unsigned>(std::min<long long>((count + 255) / 256, 256 * 64));
+  if (complexKernel)
+    hipLaunchKernelGGL((values_scale_add_kernel<T, true>), dim3(blocks), dim3(256), 0, stream, acc, in, kernel,
+                       count);
+  else
+    hipLaunchKernelGGL((values_scale_add_kernel<T, false>), dim3(blocks), dim3(256), 0, stream, acc, in, kernel,
+                       count);
+  gpu_check_launch("values_scale_add", stream);
+}
+
 }  // namespace dev
 }  // namespace spfft

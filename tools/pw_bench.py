@@ -16,7 +16,11 @@ accumulate_fock on the model's pair-density transform (the sphere |G|^2/2 <= 4
 ecut) against torch product, apply_reciprocal, torch addcmul_, with the same
 protocol and the modelled bytes of both; with --transforms T > 1 it times T
 pairs of one band per multi_transform_accumulate_fock call against the same T
-pairs as T single accumulate_fock calls into one acc, pairs per second of both.)
+pairs as T single accumulate_fock calls into one acc, pairs per second of both;
+--op gradient / divergence times PlaneWaveModel's three-component gradient and
+divergence on the density sphere, one multi_transform_reciprocal_fan_out / fan_in
+call against three apply_reciprocal calls with their copies and against the best
+composition of forward, multiply and backward, with --r2c on R2C transforms.)
 """
 import argparse
 import json
@@ -35,7 +39,8 @@ def main():
     ap.add_argument("--transforms", type=int, default=8)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--unfused", action="store_true")
-    ap.add_argument("--op", choices=("local", "density", "hartree", "fock"), default="local")
+    ap.add_argument("--op", choices=("local", "density", "hartree", "fock", "gradient", "divergence"),
+                    default="local")
     ap.add_argument("--grid", type=int, default=0,
                     help="FFT grid N^3 instead of the density grid of the cutoff (the cutoff "
                          "sphere may then reach N/2, the transforms' own minimum grid)")
@@ -49,7 +54,11 @@ def main():
     basis = PlaneWaveBasis(alat=a.alat, ecut=a.ecut,
                            fft_dims=(a.grid,) * 3 if a.grid else None)
     model = PlaneWaveModel(basis, processing_unit=sp.ProcessingUnit.GPU,
-                           num_transforms=1 if a.op == "fock" else a.transforms)
+                           num_transforms=1 if a.op in ("fock", "gradient", "divergence")
+                           else a.transforms)
+    if a.op in ("gradient", "divergence"):
+        fan(a, basis, model)
+        return
     if a.op == "fock":
         if a.transforms > 1:
             fock_multi(a, basis, model)
@@ -352,6 +361,126 @@ def fock_multi(a, basis, model):
                       "gpu_stage_median_s": stages, "host_scope_median_s": scopes,
                       "model_bytes_per_pair": model_bytes,
                       "model_ratio": model_bytes["single"] / model_bytes["multi"]}), flush=True)
+
+
+def fan(a, basis, model):
+    """--op gradient / divergence: the three components on the density sphere (the
+    pair-density transform and two clones; --r2c: R2C transforms over its hermitian half)
+    with K_d = i G_d and full scaling, three variants in alternating rounds of one process
+    (medians over at least 7 rounds):
+      fused     one multi_transform_reciprocal_fan_out / fan_in call;
+      single    three apply_reciprocal calls with the copies they need (the field copied in
+                per call; gradient: each result cloned out; divergence: the results summed
+                on the grid);
+      composed  the best composition of the existing calls: gradient, one forward, then per
+                component multiply, backward and clone; divergence, three forwards, the
+                multiply-add of the values, one backward.
+    Prints calls per second, the ratios against `fused`, the host scopes of the fused call
+    and the modelled bytes of every variant (G grid array, I intermediate, S stick array, V
+    values, K kernel; a forward or backward y+x pass G + 2 I + S, a fused z stage 2 S + K, a
+    z stage S + V, a grid copy 2 G)."""
+    import numpy as np
+    import torch
+
+    import spfft_amd as sp
+    nx, ny, nz = basis.fft_dims
+    idx = model.exchange_indices
+    unit = 2 * np.pi / basis.alat
+    if a.r2c:
+        keep = (idx[:, 0] > 0) | ((idx[:, 0] == 0) & ((idx[:, 1] > 0) |
+                                                     ((idx[:, 1] == 0) & (idx[:, 2] >= 0))))
+        idx = np.ascontiguousarray(idx[keep])
+        grid = sp.Grid(nx, ny, nz, nx * ny, sp.ProcessingUnit.GPU, 1)
+        t0 = grid.create_transform(sp.ProcessingUnit.GPU, sp.TransformType.R2C, nx, ny, nz, nz, idx)
+        ts = [t0, t0.clone(), t0.clone()]
+    else:
+        ts = model._exchange_transforms(3)
+    t = ts[0]
+    ks = [torch.as_tensor(1j * unit * idx[:, d].astype(np.float64), device="cuda") for d in range(3)]
+    g = torch.Generator(device="cuda")
+    g.manual_seed(7)
+    dtype = torch.float64 if a.r2c else torch.complex128
+    f = torch.randn((nz, ny, nx), dtype=dtype, device="cuda", generator=g)
+    hs = [torch.randn((nz, ny, nx), dtype=dtype, device="cuda", generator=g) for _ in range(3)]
+    full = sp.Scaling.FULL
+    gradient = a.op == "gradient"
+
+    def call(variant):
+        if gradient:
+            if variant == "fused":
+                return sp.multi_transform_reciprocal_fan_out(ts, ks, space=f, scaling=full)
+            if variant == "single":
+                return [t.apply_reciprocal(k, space=f, scaling=full).clone() for k in ks]
+            c = t.forward(space=f, scaling=full)
+            return [t.backward(c * k).clone() for k in ks]
+        if variant == "fused":
+            return sp.multi_transform_reciprocal_fan_in(ts, ks, spaces=hs, scaling=full)
+        if variant == "single":
+            acc = None
+            for h, k in zip(hs, ks):
+                out = t.apply_reciprocal(k, space=h, scaling=full)
+                acc = out.clone() if acc is None else acc.add_(out)
+            return acc
+        s = None
+        for h, k in zip(hs, ks):
+            c = t.forward(space=h, scaling=full)
+            s = c * k if s is None else torch.addcmul(s, c, k)
+        return t.backward(s)
+    variants = ("fused", "single", "composed")
+    rounds, calls = max(7, a.reps), 10
+    times = {v: [] for v in variants}
+    for v in variants:
+        call(v)
+    for r in range(rounds):
+        for v in (variants if r % 2 == 0 else variants[::-1]):  # mirrored orders
+            torch.cuda.synchronize()
+            t0_ = time.perf_counter()
+            for _ in range(calls):
+                call(v)
+            torch.cuda.synchronize()
+            times[v].append((time.perf_counter() - t0_) / calls)
+    med = {v: sorted(x)[len(x) // 2] for v, x in times.items()}
+    sp.timing_reset()
+    sp.timing_enable(True)
+    try:
+        for _ in range(calls):
+            call("fused")
+        torch.cuda.synchronize()
+        scopes = _scope_medians(sp.timing_json(), {
+            "multi_reciprocal_fan_out", "multi_reciprocal_fan_in", "gpu_reciprocal_fan_out_batch",
+            "gpu_reciprocal_fan_in_batch"})
+    finally:
+        sp.timing_enable(False)
+    key = idx[:, 0].astype("int64") * (2 * ny + 1) + idx[:, 1]
+    sticks = len(set(key.tolist()))
+    columns = len(set(idx[:, 0].tolist()))
+    G = nx * ny * nz * (8 if a.r2c else 16)
+    I, S, V = columns * ny * nz * 16, sticks * nz * 16, len(idx) * 16
+    K = V
+    xy = G + 2 * I + S
+    if gradient:
+        model_bytes = {"fused": 2 * G + xy + (4 * S + 3 * K) + 3 * xy,
+                       "single": 3 * (2 * G + xy + (2 * S + K) + xy + 2 * G),
+                       "composed": 2 * G + xy + (S + V) + 3 * ((2 * V + K) + (V + S) + xy + 2 * G)}
+    else:
+        model_bytes = {"fused": 3 * (2 * G + xy) + (4 * S + 3 * K) + xy,
+                       "single": 3 * (2 * G + xy + (2 * S + K) + xy) + 2 * G + 2 * 3 * G,
+                       "composed": 3 * (2 * G + xy + (S + V)) + 3 * (2 * V + K) + 2 * 3 * V + (V + S) + xy}
+    print(json.dumps({"workload": "plane-wave " + a.op, "type": "r2c" if a.r2c else "c2c",
+                      "fft_dims": list(basis.fft_dims), "num_values": len(idx), "sticks": sticks,
+                      "batch": os.environ.get("SPFFT_BATCH", "1"),
+                      "reciprocal_fused": t.reciprocal_fused,
+                      "reciprocal_fan_fused": t.reciprocal_fan_fused(3),
+                      "rounds": rounds, "calls_per_round": calls,
+                      "median_us": {v: 1e6 * x for v, x in med.items()},
+                      "min_us": {v: 1e6 * min(x) for v, x in times.items()},
+                      "ratio_single_over_fused": med["single"] / med["fused"],
+                      "ratio_composed_over_fused": med["composed"] / med["fused"],
+                      "host_scope_median_s": scopes,
+                      "model_bytes": model_bytes,
+                      "model_ratio_single": model_bytes["single"] / model_bytes["fused"],
+                      "model_ratio_composed": model_bytes["composed"] / model_bytes["fused"]}),
+          flush=True)
 
 
 if __name__ == "__main__":
