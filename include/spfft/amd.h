@@ -341,6 +341,63 @@ SPFFT_EXPORT SpfftError spfft_amd_transform_reciprocal_fan_fused(SpfftTransform 
 SPFFT_EXPORT SpfftError spfft_amd_float_transform_reciprocal_fan_fused(SpfftFloatTransform t, int n,
                                                                        int* fused);
 
+/* Value fans: one array of frequency values fans out through n reciprocal-space
+ * kernels into n transforms on distinct grids (a transform and its clones), as
+ * the kinetic-energy density and the tau-dependent term of a meta-GGA
+ * Hamiltonian need. The transforms must have equal dimensions, type, local
+ * planes and local element count: values are matched by position.
+ *
+ * Density fan:
+ *   density[z][y][x] += sum_i weights[i] * |backward_i(K_i * input)[z][y][x]|^2
+ * Apply-local fan:
+ *   output = sum_i L_i * (scale * forward_i(V_i * backward_i(K_i * input)))
+ * both in list order. input and output hold one interleaved-complex entry per
+ * local frequency value, in index order; input == output is allowed, input is
+ * otherwise not modified. kernels / kernelsIn (K_i) and kernelsOut (L_i) hold
+ * one entry per local value, all real or all interleaved complex
+ * (kernelIsComplex); a NULL entry is the identity; pointers may repeat.
+ * potentials[i] is the real potential over the local space domain as in
+ * spfft_amd_transform_apply_local; density and weights are as in
+ * spfft_amd_multi_transform_accumulate_density (density is never zeroed). All
+ * arrays are host or device pointers (weights and the pointer arrays are host
+ * arrays). The sum order is fixed by the call alone: the same call on the same
+ * data gives the same bits. The space domains are unspecified afterwards.
+ *
+ * Identical C2C plans on one GPU with simple sticks, fused x stages, device
+ * pointers, n <= 8 and z lines that fit a workgroup's LDS twice
+ * (spfft_amd_transform_values_fan_fused) run one z kernel that multiplies each
+ * stick block's values by K_i per member and writes n stick arrays, the batched y and x
+ * launches of the multi-transform calls and, for the apply-local fan, one z
+ * kernel that sums the members' L_i-weighted coefficients per stick block and
+ * stores the values once (SPFFT_BATCH). Everything else runs, per member in list
+ * order, a multiply of the values, spfft_amd_transform_apply_local /
+ * accumulate_density and a multiply-add into one buffer. n == 0 is a no-op.
+ * Collective on distributed grids (per transform, in list order). A repeated
+ * grid, a null pointer array or weights with n > 0, a null input, output or
+ * density while local values or planes exist, a null potentials[i] with local
+ * planes, unequal transforms or a bad scaling is SPFFT_INVALID_PARAMETER_ERROR;
+ * the transforms stay usable after an error. */
+SPFFT_EXPORT SpfftError spfft_amd_multi_transform_accumulate_density_fan(
+    int n, SpfftTransform* transforms, const double* input, const double* const* kernels,
+    int kernelIsComplex, const double* weights, double* density);
+SPFFT_EXPORT SpfftError spfft_amd_float_multi_transform_accumulate_density_fan(
+    int n, SpfftFloatTransform* transforms, const float* input, const float* const* kernels,
+    int kernelIsComplex, const float* weights, float* density);
+SPFFT_EXPORT SpfftError spfft_amd_multi_transform_apply_local_fan(
+    int n, SpfftTransform* transforms, const double* input, const double* const* kernelsIn,
+    const double* const* potentials, const double* const* kernelsOut, int kernelIsComplex, double* output,
+    SpfftScalingType scaling);
+SPFFT_EXPORT SpfftError spfft_amd_float_multi_transform_apply_local_fan(
+    int n, SpfftFloatTransform* transforms, const float* input, const float* const* kernelsIn,
+    const float* const* potentials, const float* const* kernelsOut, int kernelIsComplex, float* output,
+    SpfftScalingType scaling);
+/* *fused = 1 if t and n - 1 clones of it, called with device pointers, run the
+ * fused z fan kernels of the two calls above, else 0. Whether the x stage
+ * between them is fused is what spfft_amd_transform_apply_local_fused /
+ * density_fused report. */
+SPFFT_EXPORT SpfftError spfft_amd_transform_values_fan_fused(SpfftTransform t, int n, int* fused);
+SPFFT_EXPORT SpfftError spfft_amd_float_transform_values_fan_fused(SpfftFloatTransform t, int n, int* fused);
+
 /* Timer tree (SPFFT_TIMING=1 or spfft_amd_timing_enable). enable: 0 off, 1 host
  * scopes only (like the reference's timer), 2 host scopes and GPU stage times
  * (a hipEvent per stage boundary, nodes gpu/<direction>/<stage>). */

@@ -18,7 +18,8 @@ from .types import (ErrorCode, ExchangeType, IndexFormat, ProcessingUnit, Scalin
                     SpfftError, TransformType)
 from .types import *  # noqa: F401,F403  (exception classes)
 from .grid import (Grid, GridFloat, Transform, TransformFloat,  # noqa: F401
-                   multi_transform_accumulate_density, multi_transform_accumulate_fock,
+                   multi_transform_accumulate_density, multi_transform_accumulate_density_fan,
+                   multi_transform_accumulate_fock, multi_transform_apply_local_fan,
                    multi_transform_apply_local,
                    multi_transform_backward, multi_transform_forward,
                    multi_transform_reciprocal_fan_in, multi_transform_reciprocal_fan_out)

@@ -554,6 +554,16 @@ class _TransformBase:
         _check(self._prec.amd_fn("transform_reciprocal_fan_fused")(self._h, int(n), ctypes.byref(v)))
         return bool(v.value)
 
+    def values_fan_fused(self, n: int) -> bool:
+        """True if this transform and n - 1 clones of it, called with device arrays, run the
+        fused z fan kernels of multi_transform_accumulate_density_fan /
+        multi_transform_apply_local_fan (C2C plans on one GPU without exchange, simple
+        sticks, fused x stages, 1 <= n <= 8, z lines that fit a workgroup's LDS twice,
+        SPFFT_BATCH not 0)."""
+        v = ctypes.c_int()
+        _check(self._prec.amd_fn("transform_values_fan_fused")(self._h, int(n), ctypes.byref(v)))
+        return bool(v.value)
+
     def accumulate_fock(self, a, b, kernel, weight, acc, values=None, scaling=Scaling.NONE):
         """Exchange (Fock) pair operator in one call:
         acc += weight * a * backward(kernel * forward(conj(a) * b, scaling)).
@@ -940,3 +950,114 @@ def multi_transform_reciprocal_fan_in(transforms, kernels, spaces=None, location
     for t in transforms:
         t._step_keep = (keeps,)
     return transforms[0].space_domain(location)
+
+
+def _values_fan_kernels(transforms, prec, lists, what):
+    """Kernel pointer arrays of the value fans: one array per list, None entries are the
+    identity (a null pointer). Returns (pointer arrays, is_complex, keepalives)."""
+    n = len(transforms)
+    arrays, keeps, cplx = [], [], None
+    for kernels in lists:
+        if _is_torch(kernels) or isinstance(kernels, np.ndarray):
+            raise TypeError(f"{what}: kernels is a sequence of one array (or None) per transform")
+        kernels = list(kernels)
+        if len(kernels) != n:
+            raise ValueError(f"{what}: one kernel (or None) per transform")
+        ptrs, seen = (ctypes.c_void_p * max(1, n))(), {}
+        for i, t in enumerate(transforms):
+            if kernels[i] is None:
+                continue
+            first = seen.get(id(kernels[i]))
+            if first is not None:
+                ptrs[i] = ptrs[first]  # one conversion, one pointer
+                continue
+            ptrs[i], kkeep, c = _kernel_ptr(kernels[i], prec, t.num_local_elements)
+            seen[id(kernels[i])] = i
+            keeps.append(kkeep)
+            if cplx is None:
+                cplx = c
+            elif c != cplx:
+                raise TypeError("kernels of one call are all real or all complex")
+        arrays.append(ptrs)
+    return arrays, bool(cplx), keeps
+
+
+def _values_fan_common(transforms, values, what):
+    n, prec, arr = _multi(transforms)
+    if any(t._single != prec.single for t in transforms):
+        raise TypeError("transforms of one call share one precision")
+    if any(t.num_local_elements != transforms[0].num_local_elements for t in transforms):
+        raise ValueError(f"{what}: transforms of one call share one index set size")
+    if n and values is not None:
+        cnt = values.numel() if _is_torch(values) else np.asarray(values).size
+        if cnt != transforms[0].num_local_elements:
+            raise ValueError(f"values: expected {transforms[0].num_local_elements} entries, got {cnt}")
+    return n, prec, arr
+
+
+def multi_transform_accumulate_density_fan(transforms, values, kernels, weights, density):
+    """Density fan in one call: density += sum_i weights[i] * |backward_i(kernels[i] *
+    values)|**2, in list order, for one array of frequency values and one kernel per
+    transform (the kinetic-energy density with kernels i G_d).
+
+    The transforms live on distinct grids (a transform and its clones) and have equal
+    dimensions, type and index set sizes. `kernels` holds one real or complex array per
+    transform as in apply_reciprocal (all real or all complex; the same array may be given
+    several times); a None entry is the identity. `weights` and `density` are as in
+    multi_transform_accumulate_density: `density` is updated in place and never zeroed;
+    `values` is not modified. Identical fused plans on one GPU (see
+    Transform.values_fan_fused) run one z kernel that writes every member's sticks and one
+    launch per later stage. The sum order is fixed by the call. Returns `density`."""
+    n, prec, arr = _values_fan_common(transforms, values, "accumulate_density_fan")
+    if len(weights) != n:
+        raise ValueError("accumulate_density_fan: one weight per transform")
+    (kptrs,), cplx, keeps = _values_fan_kernels(transforms, prec, (kernels,), "accumulate_density_fan")
+    shape = transforms[0].space_domain_shape() if n else None
+    if any(tuple(t.space_domain_shape()) != tuple(shape) for t in transforms):
+        raise ValueError("transforms of one call share one space domain shape")
+    rptr, rkeep = _density_ptr(density, prec, shape) if n else (None, None)
+    iptr, ikeep = _data_ptr(values, prec, False, "values") if n else (None, None)
+    ws = ((ctypes.c_float if prec.single else ctypes.c_double) * max(1, n))(*[float(w) for w in weights])
+    _check(prec.amd_fn("multi_transform_accumulate_density_fan")(
+        n, arr, iptr, kptrs, 1 if cplx else 0, ctypes.cast(ws, ctypes.c_void_p), rptr))
+    # asynchronous execution (set_stream(..., synchronous=False)) may still use them
+    for t in transforms:
+        t._step_keep = (keeps, ikeep, rkeep)
+    return density
+
+
+def multi_transform_apply_local_fan(transforms, values, kernels_in, potentials, kernels_out, output=None,
+                                    scaling=Scaling.NONE):
+    """Apply-local fan in one call: output = sum_i kernels_out[i] * forward_i(potentials[i] *
+    backward_i(kernels_in[i] * values), scaling), in list order (the local part of a
+    meta-GGA Hamiltonian: member 0 with None kernels is apply_local, the others carry
+    i G_d on both sides and the potential V_tau).
+
+    Transforms, kernel lists (None entries are the identity; both lists all real or all
+    complex) and the fused path are as in multi_transform_accumulate_density_fan;
+    `potentials` holds one real array of space_domain_shape() per transform (the same
+    array may be given several times). `output` may be `values`; `values` is otherwise
+    not modified. The sum order is fixed by the call. Returns the frequency values."""
+    n, prec, arr = _values_fan_common(transforms, values, "apply_local_fan")
+    potentials = list(potentials)
+    if len(potentials) != n:
+        raise ValueError("apply_local_fan: one potential per transform")
+    (kin, kout), cplx, keeps = _values_fan_kernels(transforms, prec, (kernels_in, kernels_out),
+                                                   "apply_local_fan")
+    vptrs = (ctypes.c_void_p * max(1, n))()
+    for i, t in enumerate(transforms):
+        vptrs[i], k = _potential_ptr(potentials[i], prec, t.space_domain_shape())
+        keeps.append(k)
+    if n == 0:
+        _check(prec.amd_fn("multi_transform_apply_local_fan")(0, arr, None, kin, vptrs, kout, 0, None,
+                                                              int(scaling)))
+        return output
+    if output is None:
+        output = transforms[0]._default_output()
+    iptr, ikeep = _data_ptr(values, prec, False, "values")
+    optr, okeep = _data_ptr(output, prec, True, "output")
+    _check(prec.amd_fn("multi_transform_apply_local_fan")(
+        n, arr, iptr, kin, vptrs, kout, 1 if cplx else 0, optr, int(scaling)))
+    for t in transforms:
+        t._step_keep = (keeps, ikeep, okeep)
+    return output

@@ -367,6 +367,97 @@ class PlaneWaveModel:
             s = c if s is None else s + c
         return self._copy(t.backward(s))
 
+    def wave_gradient_kernels(self):
+        """K_d(G) = i G_d, d = x, y, z, on the wavefunction sphere |G|^2/2 <= ecut (the index
+        set of the model's transforms): complex, in the transforms' precision, where the
+        transforms run."""
+        ks = getattr(self, "_wave_gradient_kernels", None)
+        if ks is None:
+            t = self.transforms[0]
+            unit = 2 * np.pi / self.basis.alat
+            ks = [(1j * unit * self.basis.indices[:, d].astype(np.float64)).astype(t._prec.complex)
+                  for d in range(3)]
+            if self.pu == ProcessingUnit.GPU:
+                import torch
+                ks = [torch.as_tensor(k, device=f"cuda:{t.device_id}") for k in ks]
+            self._wave_gradient_kernels = ks
+        return ks
+
+    def _wave_transforms(self, count: int):
+        """`count` identical wavefunction transforms: the model's, then clones kept for the
+        value fans (the model's own list, and with it the band groups, stays as it is)."""
+        extra = getattr(self, "_wave_clones", None)
+        if extra is None:
+            extra = self._wave_clones = []
+        while len(self.transforms) + len(extra) < count:
+            extra.append(self.transforms[0].clone())
+        return (self.transforms + extra)[:count]
+
+    def _real_field(self, v):
+        real = self.transforms[0]._prec
+        if hasattr(v, "mul_"):
+            return v.to(real.torch_real).contiguous()
+        return np.ascontiguousarray(v, dtype=real.real)
+
+    def kinetic_energy_density(self, psi: Sequence, weights: Sequence[float], unfused: bool = False):
+        """tau(r) = 1/2 sum_b w_b sum_d |FFT^-1[i G_d c_b](r)|^2 on the real-space grid
+        [z][y][x], in a zeroed array of the transforms' precision where the transforms run.
+
+        One multi_transform_accumulate_density_fan call per band on three wavefunction
+        transforms (on the GPU one z kernel that reads the band's coefficients and feeds
+        three inverse z FFTs, then one launch per later stage for the three components);
+        `unfused` multiplies the coefficients by the three kernels and runs
+        multi_transform_accumulate_density."""
+        from ..grid import multi_transform_accumulate_density, multi_transform_accumulate_density_fan
+        ts = self._wave_transforms(3)
+        ks = self.wave_gradient_kernels()
+        t0 = ts[0]
+        psi, weights = list(psi), list(weights)
+        if self.pu == ProcessingUnit.GPU:
+            import torch
+            dev = psi[0].device if psi and getattr(psi[0], "is_cuda", False) else "cuda"
+            tau = torch.zeros(t0.space_domain_shape(), dtype=t0._prec.torch_real, device=dev)
+        else:
+            tau = np.zeros(t0.space_domain_shape(), dtype=t0._prec.real)
+        for c, w in zip(psi, weights):
+            if not unfused:
+                multi_transform_accumulate_density_fan(ts, c, ks, [0.5 * w] * 3, tau)
+            else:
+                multi_transform_accumulate_density(ts, [k * c for k in ks], [0.5 * w] * 3, tau)
+        return tau
+
+    def meta_gga_local(self, psi: Sequence, v_r, v_tau, unfused: bool = False) -> List:
+        """The local part of a meta-GGA Hamiltonian for every band b (band coefficients in,
+        band coefficients out): FFT[V FFT^-1[c_b]] - 1/2 sum_d i G_d FFT[V_tau FFT^-1[i G_d c_b]]
+        with the real-space potentials `v_r` and `v_tau` [z][y][x].
+
+        One multi_transform_apply_local_fan call per band on four wavefunction transforms:
+        member 0 with no kernels and V, members 1..3 with i G_d in front, V_tau and
+        -1/2 i G_d behind (on the GPU one z kernel in, the batched y and x launches, one z
+        kernel that sums the four results); `unfused` multiplies the coefficients, runs
+        multi_transform_apply_local and combines the four outputs."""
+        from ..grid import multi_transform_apply_local, multi_transform_apply_local_fan
+        ts = self._wave_transforms(4)
+        ks = self.wave_gradient_kernels()
+        ls = getattr(self, "_wave_gradient_kernels_out", None)
+        if ls is None:
+            ls = self._wave_gradient_kernels_out = [-0.5 * k for k in ks]
+        v, vt = self._real_field(v_r), self._real_field(v_tau)
+        pots = [v, vt, vt, vt]
+        out = []
+        for c in psi:
+            if not unfused:
+                out.append(self._copy(multi_transform_apply_local_fan(
+                    ts, c, [None] + ks, pots, [None] + ls, scaling=Scaling.FULL)))
+                continue
+            res = multi_transform_apply_local(ts, [c] + [k * c for k in ks], pots,
+                                              scalings=[Scaling.FULL] * 4)
+            h = self._copy(res[0])
+            for l, r in zip(ls, res[1:]):
+                h = h + l * r
+            out.append(h)
+        return out
+
     def kinetic(self, psi: Sequence) -> List:
         """T psi_b = |G|^2/2 c_G (diagonal in the plane-wave basis)."""
         g2 = self.basis.g2

@@ -61,6 +61,18 @@ void multi_reciprocal_fan_in_handles(int n, Transform** ts, SpfftProcessingUnitT
 void multi_reciprocal_fan_in_handles(int n, TransformFloat** ts, SpfftProcessingUnitType location,
                                      const float* const* kernels, bool complexKernel,
                                      SpfftScalingType scaling);
+void multi_accumulate_density_fan_handles(int n, Transform** ts, const double* input,
+                                          const double* const* kernels, bool complexKernel,
+                                          const double* weights, double* density);
+void multi_accumulate_density_fan_handles(int n, TransformFloat** ts, const float* input,
+                                          const float* const* kernels, bool complexKernel,
+                                          const float* weights, float* density);
+void multi_apply_local_fan_handles(int n, Transform** ts, const double* input, const double* const* kernelsIn,
+                                   const double* const* potentials, const double* const* kernelsOut,
+                                   bool complexKernel, double* output, SpfftScalingType scaling);
+void multi_apply_local_fan_handles(int n, TransformFloat** ts, const float* input, const float* const* kernelsIn,
+                                   const float* const* potentials, const float* const* kernelsOut,
+                                   bool complexKernel, float* output, SpfftScalingType scaling);
 }  // namespace spfft
 
 using namespace spfft;
@@ -759,6 +771,67 @@ SpfftError spfft_amd_float_transform_reciprocal_fan_fused(SpfftFloatTransform t,
   if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
   return with_handle<TransformFloat>(
       t, [&](TransformFloat& x) { *fused = x.impl()->reciprocal_fan_fused(n) ? 1 : 0; });
+}
+
+SpfftError spfft_amd_multi_transform_accumulate_density_fan(int n, SpfftTransform* transforms,
+                                                            const double* input, const double* const* kernels,
+                                                            int kernelIsComplex, const double* weights,
+                                                            double* density) {
+  if (n > 0 && !transforms) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < n; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_accumulate_density_fan_handles(n, reinterpret_cast<Transform**>(transforms), input, kernels,
+                                         kernelIsComplex != 0, weights, density);
+  });
+}
+SpfftError spfft_amd_float_multi_transform_accumulate_density_fan(int n, SpfftFloatTransform* transforms,
+                                                                  const float* input,
+                                                                  const float* const* kernels,
+                                                                  int kernelIsComplex, const float* weights,
+                                                                  float* density) {
+  if (n > 0 && !transforms) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < n; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_accumulate_density_fan_handles(n, reinterpret_cast<TransformFloat**>(transforms), input, kernels,
+                                         kernelIsComplex != 0, weights, density);
+  });
+}
+SpfftError spfft_amd_multi_transform_apply_local_fan(int n, SpfftTransform* transforms, const double* input,
+                                                     const double* const* kernelsIn,
+                                                     const double* const* potentials,
+                                                     const double* const* kernelsOut, int kernelIsComplex,
+                                                     double* output, SpfftScalingType scaling) {
+  if (n > 0 && !transforms) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < n; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_apply_local_fan_handles(n, reinterpret_cast<Transform**>(transforms), input, kernelsIn, potentials,
+                                  kernelsOut, kernelIsComplex != 0, output, scaling);
+  });
+}
+SpfftError spfft_amd_float_multi_transform_apply_local_fan(int n, SpfftFloatTransform* transforms,
+                                                           const float* input, const float* const* kernelsIn,
+                                                           const float* const* potentials,
+                                                           const float* const* kernelsOut, int kernelIsComplex,
+                                                           float* output, SpfftScalingType scaling) {
+  if (n > 0 && !transforms) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < n; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_apply_local_fan_handles(n, reinterpret_cast<TransformFloat**>(transforms), input, kernelsIn,
+                                  potentials, kernelsOut, kernelIsComplex != 0, output, scaling);
+  });
+}
+SpfftError spfft_amd_transform_values_fan_fused(SpfftTransform t, int n, int* fused) {
+  if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
+  return with_handle<Transform>(t, [&](Transform& x) { *fused = x.impl()->values_fan_fused(n) ? 1 : 0; });
+}
+SpfftError spfft_amd_float_transform_values_fan_fused(SpfftFloatTransform t, int n, int* fused) {
+  if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
+  return with_handle<TransformFloat>(
+      t, [&](TransformFloat& x) { *fused = x.impl()->values_fan_fused(n) ? 1 : 0; });
 }
 
 SpfftError spfft_amd_timing_enable(int enable) {

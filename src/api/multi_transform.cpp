@@ -540,6 +540,198 @@ void multi_reciprocal_fan_in(const std::vector<TransformImpl<T>*>& ts, SpfftProc
   ts[0]->synchronize();
 }
 
+// ------------------------------------------------------------------ value fans
+// The checks both value fans share; returns whether the fused z fan stages
+// run: GPU transforms with values_fan_fused plans and equal keys, at most
+// dev::kMaxBatch of them, device kernels. `input` and the other arrays are
+// checked by the callers.
+template <typename T>
+bool check_values_fan(const std::vector<TransformImpl<T>*>& ts, const T* const* kernelsA,
+                      const T* const* kernelsB, bool twoLists) {
+  check_distinct_grids(ts);
+  const int n = static_cast<int>(ts.size());
+  if (n > 0 && (!kernelsA || (twoLists && !kernelsB))) throw InvalidParameterError();
+  for (int i = 0; i < n; ++i) {
+    const IndexPlan& p = ts[i]->plan();
+    const IndexPlan& p0 = ts[0]->plan();
+    // values are matched by position, space domains by element
+    if (p.type != p0.type || p.dimX != p0.dimX || p.dimY != p0.dimY || p.dimZ != p0.dimZ ||
+        p.local_planes() != p0.local_planes() || p.numLocalElements != p0.numLocalElements)
+      throw InvalidParameterError();
+  }
+  if (n < 1 || n > dev::kMaxBatch) return false;
+  for (int i = 0; i < n; ++i) {
+    if (!ts[i]->is_gpu()) return false;
+    ts[i]->gpu()->ensure_stream();
+    if (!ts[i]->gpu()->values_fan_fused() || ts[i]->gpu()->batch_key() != ts[0]->gpu()->batch_key())
+      return false;
+    if (kernelsA[i] && !is_device_pointer(kernelsA[i])) return false;
+    if (twoLists && kernelsB[i] && !is_device_pointer(kernelsB[i])) return false;
+  }
+  return true;
+}
+
+// prod = K * in over the local values on g's stream (K null: in itself); the
+// array the member's backward z stage reads
+template <typename T>
+const T* fan_scaled_values(GpuExecutor<T>* g, const cx<T>* in, const T* kernel, bool complexKernel) {
+  if (!kernel) return reinterpret_cast<const T*>(in);
+  cx<T>* prod = g->fan_buffer(1);
+  g->values_scale(prod, in, kernel, complexKernel, false);
+  return reinterpret_cast<const T*>(prod);
+}
+
+// the values as a device array: `input` itself, or a copy in g's fan buffer 3
+template <typename T>
+const cx<T>* fan_device_input(GpuExecutor<T>* g, const T* input, std::size_t count) {
+  if (count == 0 || is_device_pointer(input)) return reinterpret_cast<const cx<T>*>(input);
+  cx<T>* in = g->fan_buffer(3);
+  g->copy_values(reinterpret_cast<T*>(in), input);
+  g->synchronize();  // the members' streams may read it
+  return in;
+}
+
+// density += sum_i weights[i] |backward_i(K_i * input)|^2 in list order. Fused
+// plans run GpuExecutor::accumulate_density_fan_batch; everything else the
+// composition per member in list order: a multiply of the values into a work
+// buffer (none for a null kernel), then accumulate_density, each update of rho
+// behind the previous one (device buffers when every transform is a GPU
+// transform, host buffers otherwise).
+template <typename T>
+void multi_accumulate_density_fan(const std::vector<TransformImpl<T>*>& ts, const T* input,
+                                  const T* const* kernels, bool complexKernel, const T* weights,
+                                  T* density) {
+  SPFFT_TIMED_SCOPE("multi_accumulate_density_fan");
+  bool fused = check_values_fan<T>(ts, kernels, nullptr, false);
+  const int n = static_cast<int>(ts.size());
+  if (n == 0) return;
+  if (!weights) throw InvalidParameterError();
+  const IndexPlan& p0 = ts[0]->plan();
+  const std::size_t count = static_cast<std::size_t>(p0.numLocalElements);
+  if ((count > 0 && !input) || (p0.local_planes() > 0 && !density)) throw InvalidParameterError();
+  if ((count > 0 && !is_device_pointer(input)) || (p0.local_planes() > 0 && !is_device_pointer(density)))
+    fused = false;
+  if (fused) {
+    std::vector<GpuExecutor<T>*> ex;
+    std::vector<const T*> ks;
+    std::vector<T> ws;
+    for (int i = 0; i < n; ++i) {
+      ex.push_back(ts[i]->gpu());
+      ks.push_back(kernels[i]);
+      ws.push_back(weights[i]);
+    }
+    GpuExecutor<T>::accumulate_density_fan_batch(ex, input, ks, complexKernel, ws, density);
+    for (int i = 0; i < n; ++i)
+      if (ts[i]->gpu()->synchronous()) ts[i]->synchronize();
+    return;
+  }
+  bool allGpu = true;
+  for (auto* t : ts) allGpu = allGpu && t->is_gpu();
+  if (allGpu) {
+    const cx<T>* in = fan_device_input<T>(ts[0]->gpu(), input, count);
+    for (int i = 0; i < n; ++i) {
+      ts[i]->accumulate_density(fan_scaled_values<T>(ts[i]->gpu(), in, kernels[i], complexKernel), weights[i],
+                                density);
+      ts[i]->synchronize();  // the next member's update of rho comes behind this one
+    }
+    return;
+  }
+  if (count > 0 && is_device_pointer(input)) throw InvalidParameterError();
+  std::vector<T> prod(2 * std::max<std::size_t>(count, 1));
+  for (int i = 0; i < n; ++i) {
+    if (kernels[i] && count > 0 && is_device_pointer(kernels[i])) throw InvalidParameterError();
+    const T* src = input;
+    if (kernels[i]) {
+      host_values_scale<T>(prod.data(), input, kernels[i], complexKernel, count, false);
+      src = prod.data();
+    }
+    ts[i]->accumulate_density(src, weights[i], density);
+    ts[i]->synchronize();
+  }
+}
+
+// output = sum_i L_i * (scale * forward_i(V_i * backward_i(K_i * input))) in
+// list order. Fused plans run GpuExecutor::apply_local_fan_batch; everything
+// else the composition per member in list order: a multiply of the values into
+// a work buffer, apply_local into a second one, a multiply-add into the sum
+// (null kernels skip the multiplies); `output` is written at the end, so it
+// may be `input`.
+template <typename T>
+void multi_apply_local_fan(const std::vector<TransformImpl<T>*>& ts, const T* input,
+                           const T* const* kernelsIn, const T* const* potentials,
+                           const T* const* kernelsOut, bool complexKernel, T* output,
+                           SpfftScalingType scaling) {
+  SPFFT_TIMED_SCOPE("multi_apply_local_fan");
+  bool fused = check_values_fan<T>(ts, kernelsIn, kernelsOut, true);
+  if (scaling != SPFFT_NO_SCALING && scaling != SPFFT_FULL_SCALING) throw InvalidParameterError();
+  const int n = static_cast<int>(ts.size());
+  if (n == 0) return;
+  if (!potentials) throw InvalidParameterError();
+  const IndexPlan& p0 = ts[0]->plan();
+  const std::size_t count = static_cast<std::size_t>(p0.numLocalElements);
+  if (count > 0 && (!input || !output)) throw InvalidParameterError();
+  for (int i = 0; i < n; ++i) {
+    if (p0.local_planes() > 0 && !potentials[i]) throw InvalidParameterError();
+    if (p0.local_planes() > 0 && !is_device_pointer(potentials[i])) fused = false;
+  }
+  if (count > 0 && (!is_device_pointer(input) || !is_device_pointer(output))) fused = false;
+  if (fused) {
+    std::vector<GpuExecutor<T>*> ex;
+    std::vector<const T*> kin, pots, kout;
+    for (int i = 0; i < n; ++i) {
+      ex.push_back(ts[i]->gpu());
+      kin.push_back(kernelsIn[i]);
+      pots.push_back(potentials[i]);
+      kout.push_back(kernelsOut[i]);
+    }
+    GpuExecutor<T>::apply_local_fan_batch(ex, input, kin, pots, kout, complexKernel, output, scaling);
+    for (int i = 0; i < n; ++i)
+      if (ts[i]->gpu()->synchronous()) ts[i]->synchronize();
+    return;
+  }
+  bool allGpu = true;
+  for (auto* t : ts) allGpu = allGpu && t->is_gpu();
+  if (allGpu) {
+    GpuExecutor<T>* g0 = ts[0]->gpu();
+    const cx<T>* in = fan_device_input<T>(g0, input, count);
+    cx<T>* sum = g0->fan_buffer(0);
+    for (int i = 0; i < n; ++i) {
+      GpuExecutor<T>* g = ts[i]->gpu();
+      // member 0 with the identity L writes the sum itself
+      cx<T>* res = i == 0 && !kernelsOut[i] ? sum : g->fan_buffer(2);
+      ts[i]->apply_local(fan_scaled_values<T>(g, in, kernelsIn[i], complexKernel), potentials[i],
+                         reinterpret_cast<T*>(res), scaling);
+      if (kernelsOut[i]) g->values_scale(sum, res, kernelsOut[i], complexKernel, i > 0);
+      else if (i > 0) g->values_add(sum, res);
+      ts[i]->synchronize();  // the next member's update of the sum comes behind this one
+    }
+    g0->copy_values(output, reinterpret_cast<const T*>(sum));
+    // (also in asynchronous mode: the sum is member 0's work array, which its next call reuses)
+    ts[0]->synchronize();
+    return;
+  }
+  if (count > 0 && (is_device_pointer(input) || is_device_pointer(output))) throw InvalidParameterError();
+  std::vector<T> prod(2 * std::max<std::size_t>(count, 1)), res(prod.size()), sum(prod.size());
+  for (int i = 0; i < n; ++i) {
+    if (count > 0 && ((kernelsIn[i] && is_device_pointer(kernelsIn[i])) ||
+                      (kernelsOut[i] && is_device_pointer(kernelsOut[i]))))
+      throw InvalidParameterError();
+    const T* src = input;
+    if (kernelsIn[i]) {
+      host_values_scale<T>(prod.data(), input, kernelsIn[i], complexKernel, count, false);
+      src = prod.data();
+    }
+    ts[i]->apply_local(src, potentials[i], res.data(), scaling);
+    ts[i]->synchronize();
+    if (kernelsOut[i]) {
+      host_values_scale<T>(sum.data(), res.data(), kernelsOut[i], complexKernel, count, i > 0);
+    } else {
+      for (std::size_t k = 0; k < 2 * count; ++k) sum[k] = i > 0 ? sum[k] + res[k] : res[k];
+    }
+  }
+  std::copy(sum.begin(), sum.begin() + 2 * count, output);
+}
+
 template <typename TR, typename T>
 std::vector<TransformImpl<T>*> impls(int n, TR* transforms) {
   if (n < 0 || (n > 0 && !transforms)) throw InvalidParameterError();
@@ -665,6 +857,38 @@ void multi_reciprocal_fan_in_handles(int n, TransformFloat** ts, SpfftProcessing
   std::vector<TransformImpl<float>*> v;
   for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
   multi_reciprocal_fan_in<float>(v, location, kernels, complexKernel, scaling);
+}
+void multi_accumulate_density_fan_handles(int n, Transform** ts, const double* input,
+                                          const double* const* kernels, bool complexKernel,
+                                          const double* weights, double* density) {
+  if (n < 0 || (n > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<double>*> v;
+  for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_accumulate_density_fan<double>(v, input, kernels, complexKernel, weights, density);
+}
+void multi_accumulate_density_fan_handles(int n, TransformFloat** ts, const float* input,
+                                          const float* const* kernels, bool complexKernel,
+                                          const float* weights, float* density) {
+  if (n < 0 || (n > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<float>*> v;
+  for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_accumulate_density_fan<float>(v, input, kernels, complexKernel, weights, density);
+}
+void multi_apply_local_fan_handles(int n, Transform** ts, const double* input, const double* const* kernelsIn,
+                                   const double* const* potentials, const double* const* kernelsOut,
+                                   bool complexKernel, double* output, SpfftScalingType scaling) {
+  if (n < 0 || (n > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<double>*> v;
+  for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_apply_local_fan<double>(v, input, kernelsIn, potentials, kernelsOut, complexKernel, output, scaling);
+}
+void multi_apply_local_fan_handles(int n, TransformFloat** ts, const float* input, const float* const* kernelsIn,
+                                   const float* const* potentials, const float* const* kernelsOut,
+                                   bool complexKernel, float* output, SpfftScalingType scaling) {
+  if (n < 0 || (n > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<float>*> v;
+  for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_apply_local_fan<float>(v, input, kernelsIn, potentials, kernelsOut, complexKernel, output, scaling);
 }
 void multi_forward_handles(int n, TransformFloat** ts, SpfftProcessingUnitType* in, float** out,
                            SpfftScalingType* sc) {

@@ -337,6 +337,11 @@ bool TransformImpl<T>::reciprocal_fan_fused(int n) const {
 }
 
 template <typename T>
+bool TransformImpl<T>::values_fan_fused(int n) const {
+  return gpu_ && n >= 1 && n <= dev::kMaxBatch && gpu_->values_fan_fused();
+}
+
+template <typename T>
 void TransformImpl<T>::synchronize() {
   if (gpu_) gpu_->synchronize();
 }

@@ -54,6 +54,10 @@ public:
   // run the fused z stage of multi_transform_reciprocal_fan_out / fan_in (n == 1:
   // that of apply_reciprocal)
   bool reciprocal_fan_fused(int n) const;
+  // whether this transform and n - 1 clones of it, called with device pointers,
+  // run the fused z fan stages of multi_transform_accumulate_density_fan /
+  // multi_transform_apply_local_fan
+  bool values_fan_fused(int n) const;
 
   // Exchange (Fock) pair operator: acc += weight * a * backward(K * (scale *
   // forward(conj(a) * b))) with a, b and acc over the local space domain

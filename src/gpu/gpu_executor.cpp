@@ -234,7 +234,7 @@ void GpuExecutor<T>::log_plan() const {
                "spfft[gpu rank %d/%d] %dx%dx%d %s %s: sticks=%d planes=%d columns=%d | z{%s} "
                "y{%s} x{%s}%s inter_planes=%d apply_local=%s density=%s reciprocal=%s fock=%s | exchange=%s%s plane=%s chunks=%d stick_blocks=%d "
                "steps=%zu+%zu (%.2f MB per peer) peer_writes=%d peer_offsets=[%lld, %lld] "
-               "library_streams=%d\n",
+               "library_streams=%d values_fan=%s\n",
                p.rank, p.size, p.dimX, p.dimY, p.dimZ,
                p.type == SPFFT_TRANS_R2C ? "R2C" : "C2C", dbl ? "fp64" : "fp32", p.local_sticks(),
                p.local_planes(), p.num_columns(),
@@ -245,7 +245,7 @@ void GpuExecutor<T>::log_plan() const {
                fockFused_ ? "fused" : "composed", layout_.buffered ? "buffered" : "compact",
                floatExchange_ ? "-float" : "", plane.c_str(), exchChunks_, stickBlocks_, bwdSteps_.size(),
                fwdSteps_.size(), chunkModel_ / 1e6, peerWrites_ ? 1 : 0, peerOffsetRange_[0],
-               peerOffsetRange_[1], GpuStream::live());
+               peerOffsetRange_[1], GpuStream::live(), values_fan_fused() ? "fused" : "composed");
 }
 
 template <typename T>
@@ -1781,6 +1781,41 @@ void GpuExecutor<T>::forward_batch(const std::vector<GpuExecutor*>& ex, const st
   batch_release(ex);
 }
 
+template <typename T>
+void GpuExecutor<T>::apply_local_batch_middle(dev::YArgs ya, const dev::BatchPtrs& yb, const dev::BatchPtrs& xb,
+                                              const dev::BatchPtrs& yf, bool shared) {
+  auto xa = xargs();
+  hipStream_t s = stream_;
+  ya.batch = yb;
+  dev::launch_y_backward<T, cx<T>>(ya, static_cast<const cx<T>*>(yb.in[0]),
+                                   static_cast<cx<T>*>(yb.out[0]), twY_->data<cx<T>>(), s);
+  xa.batch = xb;
+  {
+    // (the scope names the kernel variant: plain loads of a shared potential measured
+    // +1% against streaming ones at 256^3, 8 bands per call; profiles/r7/apply_local)
+    SPFFT_TIMED_SCOPE(shared ? "x_apply_shared_potential" : "x_apply_streamed_potential");
+    dev::launch_x_apply<T>(xa, static_cast<const T*>(xb.in[0]), static_cast<cx<T>*>(xb.out[0]), shared,
+                           twX_->data<cx<T>>(), s);
+  }
+  ya.batch = yf;
+  dev::launch_y_forward<T, cx<T>>(ya, static_cast<const cx<T>*>(yf.in[0]),
+                                  static_cast<cx<T>*>(yf.out[0]), twY_->data<cx<T>>(), s);
+}
+
+template <typename T>
+void GpuExecutor<T>::density_batch_middle(dev::YArgs ya, const dev::BatchPtrs& yb, const dev::BatchPtrs& xb,
+                                          const std::vector<T>& weights, T* density, GpuExecutor* after) {
+  auto xa = xargs();
+  hipStream_t s = stream_;
+  ya.batch = yb;
+  xa.batch = xb;
+  dev::launch_y_backward<T, cx<T>>(ya, static_cast<const cx<T>*>(yb.in[0]),
+                                   static_cast<cx<T>*>(yb.out[0]), twY_->data<cx<T>>(), s);
+  order_after_density(after);
+  dev::launch_x_density<T>(xa, static_cast<const cx<T>*>(xb.in[0]), density, weights.data(),
+                           twX_->data<cx<T>>(), s);
+}
+
 // One launch per stage for a batch of fused plans: z backward, y backward,
 // x apply, y forward, z forward. A potential shared by the whole batch is read
 // with the default cache policy (the later members find it in the caches).
@@ -1830,25 +1865,11 @@ void GpuExecutor<T>::apply_local_batch(const std::vector<GpuExecutor*>& ex,
   }
   auto za = l->zargs();
   auto ya = l->yargs();
-  auto xa = l->xargs();
   hipStream_t s = l->stream_;
   za.batch = zb;
   dev::launch_z_backward<T, cx<T>>(za, static_cast<const cx<T>*>(zb.in[0]),
                                    static_cast<cx<T>*>(zb.out[0]), l->twZ_->data<cx<T>>(), s);
-  ya.batch = yb;
-  dev::launch_y_backward<T, cx<T>>(ya, static_cast<const cx<T>*>(yb.in[0]),
-                                   static_cast<cx<T>*>(yb.out[0]), l->twY_->data<cx<T>>(), s);
-  xa.batch = xb;
-  {
-    // (the scope names the kernel variant: plain loads of a shared potential measured
-    // +1% against streaming ones at 256^3, 8 bands per call; profiles/r7/apply_local)
-    SPFFT_TIMED_SCOPE(shared ? "x_apply_shared_potential" : "x_apply_streamed_potential");
-    dev::launch_x_apply<T>(xa, static_cast<const T*>(xb.in[0]), static_cast<cx<T>*>(xb.out[0]), shared,
-                           l->twX_->data<cx<T>>(), s);
-  }
-  ya.batch = yf;
-  dev::launch_y_forward<T, cx<T>>(ya, static_cast<const cx<T>*>(yf.in[0]),
-                                  static_cast<cx<T>*>(yf.out[0]), l->twY_->data<cx<T>>(), s);
+  l->apply_local_batch_middle(ya, yb, xb, yf, shared);
   za.batch = zf;
   dev::launch_z_forward<T, cx<T>>(za, static_cast<const cx<T>*>(zf.in[0]),
                                   static_cast<cx<T>*>(zf.out[0]), factor, l->twZ_->data<cx<T>>(), s);
@@ -1890,18 +1911,11 @@ void GpuExecutor<T>::accumulate_density_batch(const std::vector<GpuExecutor*>& e
   }
   auto za = l->zargs();
   auto ya = l->yargs();
-  auto xa = l->xargs();
   za.batch = zb;
-  ya.batch = yb;
-  xa.batch = xb;
   hipStream_t s = l->stream_;
   dev::launch_z_backward<T, cx<T>>(za, static_cast<const cx<T>*>(zb.in[0]),
                                    static_cast<cx<T>*>(zb.out[0]), l->twZ_->data<cx<T>>(), s);
-  dev::launch_y_backward<T, cx<T>>(ya, static_cast<const cx<T>*>(yb.in[0]),
-                                   static_cast<cx<T>*>(yb.out[0]), l->twY_->data<cx<T>>(), s);
-  l->order_after_density(after);
-  dev::launch_x_density<T>(xa, static_cast<const cx<T>*>(xb.in[0]), density, weights.data(),
-                           l->twX_->data<cx<T>>(), s);
+  l->density_batch_middle(ya, yb, xb, weights, density, after);
   batch_release(ex);
 }
 
@@ -2109,7 +2123,8 @@ template <typename T>
 cx<T>* GpuExecutor<T>::fan_buffer(int which) {
   DeviceGuard guard(deviceId_);
   const std::size_t bytes = std::max<std::size_t>(1, static_cast<std::size_t>(plan_->numLocalElements)) * sizeof(cx<T>);
-  std::unique_ptr<DeviceBuffer>& b = fanBuf_[which ? 1 : 0];
+  if (which < 0 || which > 3) throw InternalError();
+  std::unique_ptr<DeviceBuffer>& b = fanBuf_[which];
   if (!b || b->bytes() < bytes) b.reset(new DeviceBuffer(bytes));
   return b->data<cx<T>>();
 }
@@ -2141,6 +2156,146 @@ void GpuExecutor<T>::download_values(T* hostDst, const cx<T>* src) {
   const std::size_t count = static_cast<std::size_t>(plan_->numLocalElements);
   if (count == 0) return;
   gpu_check(hipMemcpyAsync(hostDst, src, sizeof(cx<T>) * count, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync");
+}
+
+// ------------------------------------------------------------------ value fans
+template <typename T>
+bool GpuExecutor<T>::values_fan_fused() const {
+  return reciprocal_fan_fused() && applyFused_ && densityFused_;
+}
+
+namespace {
+template <typename T>
+T full_scale_factor(const IndexPlan& p, SpfftScalingType scaling) {
+  return scaling == SPFFT_FULL_SCALING ? static_cast<T>(1.0 / (static_cast<double>(p.dimX) * p.dimY * p.dimZ))
+                                       : T(1);
+}
+}  // namespace
+
+// The value fan-out z stage, one launch per stage in between with the members'
+// potentials, the value fan-in z stage.
+template <typename T>
+void GpuExecutor<T>::apply_local_fan_batch(const std::vector<GpuExecutor*>& ex, const T* input,
+                                           const std::vector<const T*>& kernelsIn,
+                                           const std::vector<const T*>& potentials,
+                                           const std::vector<const T*>& kernelsOut, bool complexKernel,
+                                           T* output, SpfftScalingType scaling) {
+  SPFFT_TIMED_SCOPE("gpu_apply_local_fan_batch");
+  const int n = static_cast<int>(ex.size());
+  if (n < 1 || n > dev::kMaxBatch || kernelsIn.size() != ex.size() || potentials.size() != ex.size() ||
+      kernelsOut.size() != ex.size())
+    throw InternalError();
+  GpuExecutor* l = ex[0];
+  DeviceGuard guard(l->deviceId_);
+  for (GpuExecutor* e : ex)
+    if (!e->values_fan_fused() || e->batchKey_ != l->batchKey_) throw InternalError();
+  const IndexPlan& p = *l->plan_;
+  if (p.numLocalElements > 0 &&
+      (!input || !is_device_pointer(input) || !output || !is_device_pointer(output)))
+    throw InvalidParameterError();
+  dev::BatchPtrs zo{}, yb{}, xb{}, yf{}, zi{};
+  zo.count = yb.count = xb.count = yf.count = zi.count = n;
+  bool shared = true;
+  for (int i = 0; i < n; ++i) {
+    GpuExecutor* e = ex[i];
+    if ((kernelsIn[i] && !is_device_pointer(kernelsIn[i])) || (kernelsOut[i] && !is_device_pointer(kernelsOut[i])))
+      throw InvalidParameterError();
+    if (p.local_planes() > 0 && (!potentials[i] || !is_device_pointer(potentials[i])))
+      throw InvalidParameterError();
+    shared = shared && potentials[i] == potentials[0];
+    void* stick = e->grid_->device_slot(GridImpl<T>::kStickSide);
+    void* slab = e->grid_->device_slot(GridImpl<T>::kSlabSide);
+    void* inter = e->grid_->device_slot(GridImpl<T>::kInter);
+    zo.in[i] = kernelsIn[i];
+    zo.out[i] = stick;
+    yb.in[i] = slab;
+    yb.out[i] = inter;
+    xb.in[i] = potentials[i];
+    xb.out[i] = inter;
+    yf.in[i] = inter;
+    yf.out[i] = slab;
+    zi.in[i] = kernelsOut[i];
+    zi.out[i] = stick;
+  }
+  batch_join(ex);
+  auto za = l->zargs();
+  auto ya = l->yargs();
+  hipStream_t s = l->stream_;
+  l->stage_mark("backward", nullptr);
+  za.batch = zo;
+  za.plainSticks = l->plainHandoff_;
+  dev::launch_z_values_fan_out<T>(za, complexKernel, reinterpret_cast<const cx<T>*>(input),
+                                  l->twZ_->data<cx<T>>(), s);
+  l->stage_mark("backward", "z_fan_out");
+  ya.plainSticks = l->plainHandoff_;
+  l->apply_local_batch_middle(ya, yb, xb, yf, shared);
+  l->stage_mark("backward", "y+x_apply+y");
+  za.batch = zi;
+  dev::launch_z_values_fan_in<T>(za, complexKernel, reinterpret_cast<cx<T>*>(output),
+                                 full_scale_factor<T>(p, scaling), l->twZ_->data<cx<T>>(), s);
+  l->stage_mark("backward", "z_fan_in");
+  batch_release(ex);
+}
+
+// The value fan-out z stage, then one y backward launch and one x density
+// launch whose workgroups loop over the members for their tile of rho.
+template <typename T>
+void GpuExecutor<T>::accumulate_density_fan_batch(const std::vector<GpuExecutor*>& ex, const T* input,
+                                                  const std::vector<const T*>& kernels, bool complexKernel,
+                                                  const std::vector<T>& weights, T* density,
+                                                  GpuExecutor* after) {
+  SPFFT_TIMED_SCOPE("gpu_accumulate_density_fan_batch");
+  const int n = static_cast<int>(ex.size());
+  if (n < 1 || n > dev::kMaxBatch || kernels.size() != ex.size() || weights.size() != ex.size())
+    throw InternalError();
+  GpuExecutor* l = ex[0];
+  DeviceGuard guard(l->deviceId_);
+  for (GpuExecutor* e : ex)
+    if (!e->values_fan_fused() || e->batchKey_ != l->batchKey_) throw InternalError();
+  const IndexPlan& p = *l->plan_;
+  if (p.numLocalElements > 0 && (!input || !is_device_pointer(input))) throw InvalidParameterError();
+  if (p.local_planes() > 0 && (!density || !is_device_pointer(density))) throw InvalidParameterError();
+  dev::BatchPtrs zo{}, yb{}, xb{};
+  zo.count = yb.count = xb.count = n;
+  for (int i = 0; i < n; ++i) {
+    GpuExecutor* e = ex[i];
+    if (kernels[i] && !is_device_pointer(kernels[i])) throw InvalidParameterError();
+    zo.in[i] = kernels[i];
+    zo.out[i] = e->grid_->device_slot(GridImpl<T>::kStickSide);
+    yb.in[i] = e->grid_->device_slot(GridImpl<T>::kSlabSide);
+    yb.out[i] = e->grid_->device_slot(GridImpl<T>::kInter);
+    xb.in[i] = yb.out[i];
+    xb.out[i] = nullptr;  // the members share `density`
+  }
+  batch_join(ex);
+  auto za = l->zargs();
+  auto ya = l->yargs();
+  l->stage_mark("backward", nullptr);
+  za.batch = zo;
+  za.plainSticks = l->plainHandoff_;
+  dev::launch_z_values_fan_out<T>(za, complexKernel, reinterpret_cast<const cx<T>*>(input),
+                                  l->twZ_->data<cx<T>>(), l->stream_);
+  l->stage_mark("backward", "z_fan_out");
+  ya.plainSticks = l->plainHandoff_;
+  l->density_batch_middle(ya, yb, xb, weights, density, after);
+  l->stage_mark("backward", "y+x_density");
+  batch_release(ex);
+}
+
+template <typename T>
+void GpuExecutor<T>::values_add(cx<T>* acc, const cx<T>* in) {
+  DeviceGuard guard(deviceId_);
+  order_after_default_stream();
+  dev::launch_values_add<T>(acc, in, static_cast<long long>(plan_->numLocalElements), stream_);
+}
+
+template <typename T>
+void GpuExecutor<T>::copy_values(T* dst, const T* src) {
+  DeviceGuard guard(deviceId_);
+  const std::size_t count = static_cast<std::size_t>(plan_->numLocalElements);
+  if (count == 0 || dst == src) return;
+  order_after_default_stream();
+  gpu_check(hipMemcpyAsync(dst, src, sizeof(cx<T>) * count, hipMemcpyDefault, stream_), "hipMemcpyAsync");
 }
 
 template class GpuExecutor<double>;

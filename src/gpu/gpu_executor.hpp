@@ -143,12 +143,40 @@ public:
                                        bool complexKernel, T* values, SpfftScalingType scaling);
   static void reciprocal_fan_in_batch(const std::vector<GpuExecutor*>& ex, const std::vector<const T*>& kernels,
                                       bool complexKernel, SpfftScalingType scaling);
-  // Pieces of the composed fan paths, on this executor's stream: two device
+  // Pieces of the composed fan paths, on this executor's stream: four device
   // work arrays of numLocalElements values, out = in * K or out += in * K over
   // the values (K a host or device pointer), and a copy of values to the host.
-  cx<T>* fan_buffer(int which);
+  cx<T>* fan_buffer(int which);  // which = 0 .. 3
   void values_scale(cx<T>* out, const cx<T>* in, const T* kernel, bool complexKernel, bool add);
   void download_values(T* hostDst, const cx<T>* src);
+
+  // Value fans (multi_transform_apply_local_fan / accumulate_density_fan) of
+  // batchable() C2C plans with simple sticks, fused x stages, equal keys and a z
+  // line region that fits a workgroup's LDS twice (values_fan_fused), on the
+  // leader's stream; every array is a device pointer, a null kernel is the
+  // identity. apply_local_fan_batch: the value fan-out z stage (per member
+  // K_m * input and an inverse z FFT into its stick side), the batched y
+  // backward, x apply and y forward launches of apply_local_batch with the
+  // members' potentials, and the value fan-in z stage (the members' forward z
+  // FFTs, L_m-weighted and summed in member order in LDS, one store to output).
+  // accumulate_density_fan_batch: the fan-out z stage, then the batched y
+  // backward and x density launches of accumulate_density_batch. The space
+  // domains are untouched.
+  bool values_fan_fused() const;
+  static void apply_local_fan_batch(const std::vector<GpuExecutor*>& ex, const T* input,
+                                    const std::vector<const T*>& kernelsIn,
+                                    const std::vector<const T*>& potentials,
+                                    const std::vector<const T*>& kernelsOut, bool complexKernel, T* output,
+                                    SpfftScalingType scaling);
+  static void accumulate_density_fan_batch(const std::vector<GpuExecutor*>& ex, const T* input,
+                                           const std::vector<const T*>& kernels, bool complexKernel,
+                                           const std::vector<T>& weights, T* density,
+                                           GpuExecutor* after = nullptr);
+  // Pieces of the composed value fans, on this executor's stream: acc += in over
+  // the values, and a copy of numLocalElements values between host or device
+  // arrays.
+  void values_add(cx<T>* acc, const cx<T>* in);
+  void copy_values(T* dst, const T* src);
 
   void synchronize();
   bool synchronous() const { return synchronous_; }
@@ -188,11 +216,17 @@ private:
   std::unique_ptr<DeviceBuffer> density_;  // stages a host rho
   bool densityFused_ = false;
   void order_after_density(GpuExecutor* prev);  // this stream waits for prev's work so far
+  // the launches between the z stages of apply_local_batch / accumulate_density_batch
+  // (y backward, x apply, y forward; y backward, x density) on this leader's stream
+  void apply_local_batch_middle(dev::YArgs ya, const dev::BatchPtrs& yb, const dev::BatchPtrs& xb,
+                                const dev::BatchPtrs& yf, bool sharedPotential);
+  void density_batch_middle(dev::YArgs ya, const dev::BatchPtrs& yb, const dev::BatchPtrs& xb,
+                            const std::vector<T>& weights, T* density, GpuExecutor* after);
   std::unique_ptr<GpuEvent> densityEvent_;
   bool reciprocalFused_ = false;
   std::unique_ptr<DeviceBuffer> recKernel_;  // stages a host kernel
   mutable int fanFits_ = -1;  // z line region fits the LDS twice (-1: not yet asked)
-  std::unique_ptr<DeviceBuffer> fanBuf_[2];
+  std::unique_ptr<DeviceBuffer> fanBuf_[4];
   bool fockFused_ = false;
   std::unique_ptr<DeviceBuffer> fockA_, fockB_, fockAcc_;  // stage host a, b, acc
   std::size_t space_elements() const;  // elements of the local space domain

@@ -224,6 +224,25 @@ void launch_z_reciprocal_fan_in(const ZArgs& a, bool complexKernel, T scale, con
 template <typename T>
 void launch_values_scale_add(cx<T>* acc, const cx<T>* in, const T* kernel, bool complexKernel, long long count,
                              hipStream_t stream);
+// Value fan-out and fan-in z stages (multi_transform_accumulate_density_fan /
+// multi_transform_apply_local_fan; simple sticks, C2C, batch.count members with
+// identical plans; member m's stick array is ZArgs::batch.out[m], its kernel
+// batch.in[m], null for the identity). Fan-out: per member the inverse z FFT of
+// K_m * values into its stick array, the members spread over the grid like a
+// batched backward z stage (the LDS of that stage; every member's workgroups
+// read the values). Fan-in: one workgroup per stick block loops over the
+// members: the sum, in order, of L_m * scale * forward z FFT of their sticks,
+// stored once to `output`; the sum lives in a second LDS region, so the launch
+// needs z_reciprocal_fan_fits (the launcher throws otherwise).
+template <typename T>
+void launch_z_values_fan_out(const ZArgs& a, bool complexKernel, const cx<T>* values, const cx<T>* tw,
+                             hipStream_t stream);
+template <typename T>
+void launch_z_values_fan_in(const ZArgs& a, bool complexKernel, cx<T>* output, T scale, const cx<T>* tw,
+                            hipStream_t stream);
+// acc[i] += in[i] over sparse values (composed value fan, identity kernel).
+template <typename T>
+void launch_values_add(cx<T>* acc, const cx<T>* in, long long count, hipStream_t stream);
 // Composed path, one pass each: space[i] = conj(a[i]) * b[i] and acc[i] +=
 // weight * a[i] * space[i] (interleaved complex or, realSpace, real arrays).
 template <typename T>

@@ -1791,6 +1791,207 @@ __global__ void __launch_bounds__(Eng::kBlock)
   });
 }
 
+// Value fan-out z stage (multi_transform_accumulate_density_fan / apply_local_fan,
+// simple sticks, C2C): one set of frequency values feeds an inverse z FFT per
+// member. A workgroup owns a block of sticks of one member m = blockIdx.z (the
+// grid of the batched backward z stage): its line region gets K_m * value on
+// the sparse set and zero elsewhere (K_m = ZArgs::batch.in[m]; null is the
+// identity, a branch that is uniform over the workgroup), and the inverse FFT
+// stores to the member's stick array ZArgs::batch.out[m]. The members'
+// workgroups read the same values (a few KB per block, from L2 or the Infinity
+// Cache after the first), so nothing is parked in a second LDS region and the
+// kernel keeps the LDS footprint of the backward z stage. A loop over the
+// members inside one workgroup was measured first and lost to the composition
+// on small grids, where few workgroups each ran the members' FFTs one after
+// another (profiles/r13/values_fan). `values` is only read and no stick array
+// is read. There is no hermitian fill: the dispatch takes this path for C2C
+// plans only. Compile-time engines load K_m * value into the registers of the
+// first FFT pass (the fast path of z_backward_desc_kernel); run-time and
+// Bluestein engines fill the line region in LDS first.
+constexpr int kFanOutUnroll = 4;  // value and kernel loads in flight per lane
+template <class Eng, typename T, bool Cplx, bool Plain>
+__global__ void __launch_bounds__(Eng::kBlock)
+    z_values_fan_out_kernel(Eng eng, ZArgs a, const cx<T>* __restrict__ values, const cx<T>* __restrict__ tw) {
+  SPFFT_LDS_DECL(T);
+  const int m = blockIdx.z;  // < a.batch.count (the launcher's grid)
+  cx<T>* __restrict__ sticks = static_cast<cx<T>*>(a.batch.out[m]);
+  const T* __restrict__ kern = static_cast<const T*>(a.batch.in[m]);
+  const bool ident = kern == nullptr;
+  const int B = eng.lines();
+  const int n = eng.n();
+  const int s0 = a.stickBegin + block_tile_x() * B;
+  const int nl = min(B, a.numSticks - s0);
+  const ZSeg seg(a.single, a.stickStride, a.zTab,
+                 reinterpret_cast<char*>(lds) + zseg_lds_offset(eng.lds_bytes(), B), n);
+  auto store = [&](int b, int pos, cx<T> x) {
+    if (b < nl) st_stick<Plain>(&sticks[seg.at(s0 + b, pos)], x);
+  };
+  StickDesc* d = reinterpret_cast<StickDesc*>(reinterpret_cast<char*>(lds) + eng.lds_bytes());
+  for (int b = threadIdx.x; b < nl; b += blockDim.x) d[b] = a.desc[s0 + b];
+  __syncthreads();
+  if constexpr (!Eng::kBatchedCopy) {
+    // the lane's own stick descriptor in registers, as in z_backward_desc_kernel
+    const int lb = Eng::F::lane_line();
+    StickDesc q = d[lb < nl ? lb : 0];
+    int z0 = q.z0, len0 = q.len0, z1 = q.z1, len1 = q.count - q.len0, vs = q.valueStart;
+    if (lb >= nl) len0 = len1 = 0;
+    asm volatile("" : "+v"(z0), "+v"(len0), "+v"(z1), "+v"(len1), "+v"(vs));
+    const cx<T>* vals = values + vs;
+    eng.global_to_global(lds, tw, [&](int, int z) -> cx<T> {
+      const unsigned j0 = static_cast<unsigned>(z - z0), j1 = static_cast<unsigned>(z - z1);
+      const bool in0 = j0 < static_cast<unsigned>(len0);
+      const bool in1 = j1 < static_cast<unsigned>(len1);
+      if (!(in0 || in1)) return czero<T>();
+      const int j = in0 ? static_cast<int>(j0) : len0 + static_cast<int>(j1);
+      // (default cache policy: the other members' workgroups read the same values)
+      const cx<T> v = ld_values(&vals[j]);
+      if (ident) return v;
+      const cx<T> w = ld_kernel<T, Cplx>(kern, vs + j);
+      if constexpr (Cplx) return cmul(v, w);
+      else return spfft::scale(v, w.x);
+    }, store);
+  } else {
+    const int total = B * n;
+    for (int base = threadIdx.x; base < total; base += blockDim.x * kFanOutUnroll) {
+      cx<T> w[kFanOutUnroll], v[kFanOutUnroll];
+      int vi[kFanOutUnroll];
+#pragma unroll
+      for (int u = 0; u < kFanOutUnroll; ++u) {
+        const int idx = base + u * static_cast<int>(blockDim.x);
+        vi[u] = -1;
+        if (idx < total) {
+          const int b = idx / n, z = idx - b * n;
+          if (b < nl) {
+            const StickDesc& q = d[b];
+            const int j = desc_offset(q, z);
+            if (j >= 0) {
+              vi[u] = q.valueStart + j;
+              v[u] = ld_values(&values[vi[u]]);
+              if (!ident) w[u] = ld_kernel<T, Cplx>(kern, vi[u]);
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kFanOutUnroll; ++u) {
+        const int idx = base + u * static_cast<int>(blockDim.x);
+        if (idx < total) {
+          const int b = idx / n, z = idx - b * n;
+          cx<T> r = czero<T>();
+          if (vi[u] >= 0) {
+            if (ident) r = v[u];
+            else if constexpr (Cplx) r = cmul(v[u], w[u]);
+            else r = spfft::scale(v[u], w[u].x);
+          }
+          lds[eng.in_at(b, z)] = r;
+        }
+      }
+    }
+    __syncthreads();
+    eng.lds_to_global(lds, tw, store);
+  }
+}
+
+// Value fan-in z stage (multi_transform_apply_local_fan): per member m in list
+// order the forward z FFT of the block's sticks of ZArgs::batch.out[m], then
+// acc += L_m * (scale * coefficient) on the sparse set (L_m = ZArgs::batch.in[m];
+// null is the identity); after the loop one coalesced store of acc to `output`
+// through the stick descriptors. There is no inverse FFT. `acc` is a second LDS
+// region behind the launch's other LDS (byte offset accOffset), element (b, z)
+// at acc[b * n + z], with the lane ownership of z_reciprocal_fan_in_kernel: lane
+// idx of the walk owns acc[idx] in every member's walk and in the store, so
+// there are no atomics and no race, and the sum order is the member order. The
+// stick arrays are only read.
+template <class Eng, class Fwd, typename T, bool Cplx>
+__global__ void __launch_bounds__(Eng::kBlock)
+    z_values_fan_in_kernel(Eng eng, Fwd fwd, ZArgs a, cx<T>* __restrict__ output, T scale, int accOffset,
+                           const cx<T>* __restrict__ tw) {
+  SPFFT_LDS_DECL(T);
+  cx<T>* acc = reinterpret_cast<cx<T>*>(spfftSmem + accOffset);
+  const int members = pin_uniform(a.batch.count);
+  const int B = eng.lines();
+  const int n = eng.n();
+  const int s0 = a.stickBegin + block_tile_x() * B;
+  const int nl = min(B, a.numSticks - s0);
+  const ZSeg seg(a.single, a.stickStride, a.zTab,
+                 reinterpret_cast<char*>(lds) + zseg_lds_offset(eng.lds_bytes(), B), n);
+  StickDesc* d = reinterpret_cast<StickDesc*>(reinterpret_cast<char*>(lds) + eng.lds_bytes());
+  for (int b = threadIdx.x; b < nl; b += blockDim.x) d[b] = a.desc[s0 + b];
+  const int total = B * n;
+  for (int m = 0; m < members; ++m) {
+    const cx<T>* __restrict__ src = static_cast<const cx<T>*>(a.batch.out[m]);
+    const T* __restrict__ kern = static_cast<const T*>(a.batch.in[m]);
+    const bool ident = kern == nullptr;
+    // the previous member's walk has read its coefficients before these lines are reused
+    if (m > 0) __syncthreads();
+    // opaque per member, as in the fan-out kernel
+    const cx<T>* twm = tw;
+    int s0m = s0;
+    asm volatile("" : "+s"(twm), "+s"(s0m));
+    // result at fwd.out_at(b, z); ends with a barrier (which also publishes d)
+    fwd.global_to_lds(lds, twm, [&](int b, int pos) -> cx<T> {
+      if (b >= nl) return czero<T>();
+      return ld_stream(&src[seg.at(s0m + b, pos)]);
+    });
+    for (int base = threadIdx.x; base < total; base += blockDim.x * kApplyUnroll) {
+      cx<T> w[kApplyUnroll];
+      int vi[kApplyUnroll];
+#pragma unroll
+      for (int u = 0; u < kApplyUnroll; ++u) {
+        const int idx = base + u * static_cast<int>(blockDim.x);
+        vi[u] = -1;
+        if (idx < total) {
+          const int b = idx / n, z = idx - b * n;
+          if (b < nl) {
+            const StickDesc& q = d[b];
+            const int j = desc_offset(q, z);
+            if (j >= 0) {
+              vi[u] = q.valueStart + j;
+              if (!ident) w[u] = ld_kernel<T, Cplx>(kern, vi[u]);
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kApplyUnroll; ++u) {
+        const int idx = base + u * static_cast<int>(blockDim.x);
+        if (idx < total) {
+          const int b = idx / n, z = idx - b * n;
+          cx<T> r = czero<T>();
+          if (vi[u] >= 0) {
+            const cx<T> c = spfft::scale(lds[fwd.out_at(b, z)], scale);
+            if (ident) r = c;
+            else if constexpr (Cplx) r = cmul(c, w[u]);
+            else r = spfft::scale(c, w[u].x);
+          }
+          if (m > 0) {
+            const cx<T> s = acc[idx];
+            r = mk<T>(s.x + r.x, s.y + r.y);
+          }
+          acc[idx] = r;
+        }
+      }
+    }
+  }
+  // every lane stores the elements of acc it owns: no barrier in between
+  for (int idx = threadIdx.x; idx < total; idx += blockDim.x) {
+    const int b = idx / n, z = idx - b * n;
+    if (b < nl) {
+      const StickDesc& q = d[b];
+      const int j = desc_offset(q, z);
+      if (j >= 0) st_values(&output[q.valueStart + j], acc[idx]);
+    }
+  }
+}
+
+// acc[i] += in[i] over `count` sparse values (composed value fan, identity L).
+template <typename T>
+__global__ void __launch_bounds__(256) values_add_kernel(cx<T>* acc, const cx<T>* __restrict__ in, long long count) {
+  const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
+  for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride)
+    acc[i] = mk<T>(acc[i].x + in[i].x, acc[i].y + in[i].y);
+}
+
 // acc[i] += in[i] * K[i] over `count` sparse values (the composed fan-in path).
 template <typename T, bool Cplx>
 __global__ void __launch_bounds__(256)

@@ -476,6 +476,62 @@ void launch_z_reciprocal_fan_in(const ZArgs& a, bool complexKernel, T scale, con
   });
 }
 
+// Value fan-out / fan-in z stages. Fan-out: the launch of launch_z_backward
+// (its LDS), one grid plane per member (blockIdx.z, also for one member).
+// Fan-in: the unbatched grid, the workgroups loop over the batch.count
+// members, plus the second LDS region of the reciprocal fans for the sum
+// (fan_lds_bytes; z_reciprocal_fan_fits is its fit test).
+template <typename T>
+void launch_z_values_fan_out(const ZArgs& a, bool complexKernel, const cx<T>* values, const cx<T>* tw,
+                             hipStream_t stream) {
+  if (a.numSticks <= a.stickBegin || a.batch.count < 1 || a.batch.count > kMaxBatch) return;
+  if (!a.desc) throw InternalError();
+  with_engine<T, +1>(a.n, [&](auto eng, int threads, int lines, std::size_t lds) {
+    using E = decltype(eng);
+    const bool plain = a.plainSticks != 0;
+    auto k = complexKernel ? (plain ? z_values_fan_out_kernel<E, T, true, true>
+                                    : z_values_fan_out_kernel<E, T, true, false>)
+                           : (plain ? z_values_fan_out_kernel<E, T, false, true>
+                                    : z_values_fan_out_kernel<E, T, false, false>);
+    std::size_t ldsTotal = 0;
+    const ZArgs b = z_args_for_lds(a, lds, lines, &ldsTotal);
+    prepare_kernel(k, ldsTotal);
+    hipLaunchKernelGGL(k, dim3(ceil_div(a.numSticks - a.stickBegin, lines), 1, static_cast<unsigned>(a.batch.count)),
+                       dim3(threads), ldsTotal, stream, eng, b, values, tw);
+    gpu_check_launch("z_values_fan_out", stream);
+  });
+}
+
+template <typename T>
+void launch_z_values_fan_in(const ZArgs& a, bool complexKernel, cx<T>* output, T scale, const cx<T>* tw,
+                            hipStream_t stream) {
+  if (a.numSticks <= a.stickBegin || a.batch.count < 1 || a.batch.count > kMaxBatch) return;
+  if (!a.desc) throw InternalError();
+  with_engine<T, +1>(a.n, [&](auto eng, int threads, int lines, std::size_t lds) {
+    auto fwd = forward_twin(eng);
+    using E = decltype(eng);
+    using F = decltype(fwd);
+    auto k = complexKernel ? z_values_fan_in_kernel<E, F, T, true> : z_values_fan_in_kernel<E, F, T, false>;
+    std::size_t ldsTotal = 0;
+    const ZArgs b = z_args_for_lds(a, lds, lines, &ldsTotal);
+    const std::size_t bytes = fan_lds_bytes<T>(ldsTotal, lines, a.n);
+    if (bytes > kFanLdsLimit) throw InternalError();
+    prepare_kernel(k, bytes);
+    hipLaunchKernelGGL(k, dim3(ceil_div(a.numSticks - a.stickBegin, lines)), dim3(threads), bytes, stream, eng, fwd,
+                       b, output, scale, static_cast<int>(fan_hold_offset(ldsTotal)), tw);
+    gpu_check_launch("z_values_fan_in", stream);
+  });
+}
+
+// acc[i] += in[i] over `count` sparse values (composed value fan, identity L)
+template <typename T>
+void launch_values_add(cx<T>* acc, const cx<T>* in, long long count, hipStream_t stream) {
+  if (count <= 0) return;
+  const unsigned blocks = static_cast<unsigned>(std::min<long long>((count + 255) / 256, 256 * 64));
+  hipLaunchKernelGGL((values_add_kernel<T>), dim3(blocks), dim3(256), 0, stream, acc, in, count);
+  gpu_check_launch("values_add", stream);
+}
+
 // acc[i] += in[i] * kernel[i] over `count` sparse values (composed fan-in path)
 template <typename T>
 void launch_values_scale_add(cx<T>* acc, const cx<T>* in, const T* kernel, bool complexKernel, long long count,

@@ -20,7 +20,11 @@ pairs as T single accumulate_fock calls into one acc, pairs per second of both;
 --op gradient / divergence times PlaneWaveModel's three-component gradient and
 divergence on the density sphere, one multi_transform_reciprocal_fan_out / fan_in
 call against three apply_reciprocal calls with their copies and against the best
-composition of forward, multiply and backward, with --r2c on R2C transforms.)
+composition of forward, multiply and backward, with --r2c on R2C transforms;
+--op tau / mgga times the kinetic-energy density and the local meta-GGA operator
+of one band on the wavefunction sphere, one multi_transform_accumulate_density_fan
+/ multi_transform_apply_local_fan call against the best composition of torch
+multiplies and multi_transform_accumulate_density / multi_transform_apply_local.)
 """
 import argparse
 import json
@@ -39,8 +43,8 @@ def main():
     ap.add_argument("--transforms", type=int, default=8)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--unfused", action="store_true")
-    ap.add_argument("--op", choices=("local", "density", "hartree", "fock", "gradient", "divergence"),
-                    default="local")
+    ap.add_argument("--op", choices=("local", "density", "hartree", "fock", "gradient", "divergence",
+                                     "tau", "mgga"), default="local")
     ap.add_argument("--grid", type=int, default=0,
                     help="FFT grid N^3 instead of the density grid of the cutoff (the cutoff "
                          "sphere may then reach N/2, the transforms' own minimum grid)")
@@ -54,8 +58,11 @@ def main():
     basis = PlaneWaveBasis(alat=a.alat, ecut=a.ecut,
                            fft_dims=(a.grid,) * 3 if a.grid else None)
     model = PlaneWaveModel(basis, processing_unit=sp.ProcessingUnit.GPU,
-                           num_transforms=1 if a.op in ("fock", "gradient", "divergence")
+                           num_transforms=1 if a.op in ("fock", "gradient", "divergence", "tau", "mgga")
                            else a.transforms)
+    if a.op in ("tau", "mgga"):
+        values_fan(a, basis, model)
+        return
     if a.op in ("gradient", "divergence"):
         fan(a, basis, model)
         return
@@ -479,6 +486,109 @@ def fan(a, basis, model):
                       "host_scope_median_s": scopes,
                       "model_bytes": model_bytes,
                       "model_ratio_single": model_bytes["single"] / model_bytes["fused"],
+                      "model_ratio_composed": model_bytes["composed"] / model_bytes["fused"]}),
+          flush=True)
+
+
+def values_fan(a, basis, model):
+    """--op tau / mgga: one band on the wavefunction sphere with K_d = i G_d, two variants in
+    alternating rounds of one process (medians over at least 7 rounds):
+      fused     tau: one multi_transform_accumulate_density_fan call on three transforms;
+                mgga: one multi_transform_apply_local_fan call on four transforms, member 0
+                with None kernels and V, members 1..3 with i G_d, V_tau and -1/2 i G_d;
+      composed  the best composition of the existing calls: tau, three torch multiplies of
+                the values and one multi_transform_accumulate_density call; mgga, three
+                multiplies, one multi_transform_apply_local call of four members and three
+                torch.addcmul of the outputs.
+    Prints microseconds per call, the ratio, the host scopes of the fused call and the
+    modelled bytes of both (V values, K kernel, S stick array, I intermediate, R real grid
+    array; a z stage V + S, a fan z stage V + sum of (K + S) with the values counted once, a
+    y stage S + I, the x density stage I per member and 2 R, the x apply stage 2 I + R, a
+    torch multiply 2 V + K, an addcmul 3 V + K)."""
+    import numpy as np
+    import torch
+
+    import spfft_amd as sp
+    nx, ny, nz = basis.fft_dims
+    idx = basis.indices
+    tau = a.op == "tau"
+    n = 3 if tau else 4
+    ts = model._wave_transforms(n)
+    t = ts[0]
+    ks = model.wave_gradient_kernels()
+    ls = [-0.5 * k for k in ks]
+    g = torch.Generator(device="cuda")
+    g.manual_seed(9)
+    c = torch.randn(basis.num_pw, dtype=torch.complex128, device="cuda", generator=g)
+    v_r, v_tau = (torch.rand((nz, ny, nx), dtype=torch.float64, device="cuda", generator=g) for _ in range(2))
+    rho = torch.zeros((nz, ny, nx), dtype=torch.float64, device="cuda")
+    out = torch.empty_like(c)
+    pots = [v_r, v_tau, v_tau, v_tau]
+    ws = [0.5] * 3
+    full = sp.Scaling.FULL
+
+    def call(variant):
+        if tau:
+            if variant == "fused":
+                return sp.multi_transform_accumulate_density_fan(ts, c, ks, ws, rho)
+            return sp.multi_transform_accumulate_density(ts, [k * c for k in ks], ws, rho)
+        if variant == "fused":
+            return sp.multi_transform_apply_local_fan(ts, c, [None] + ks, pots, [None] + ls, output=out,
+                                                      scaling=full)
+        res = sp.multi_transform_apply_local(ts, [c] + [k * c for k in ks], pots, scalings=[full] * 4)
+        h = res[0]
+        for l, r in zip(ls, res[1:]):
+            h = torch.addcmul(h, l, r)
+        return h
+    variants = ("fused", "composed")
+    rounds, calls = max(7, a.reps), 10
+    times = {v: [] for v in variants}
+    for v in variants:
+        call(v)
+    for r in range(rounds):
+        for v in (variants if r % 2 == 0 else variants[::-1]):  # mirrored orders
+            torch.cuda.synchronize()
+            t0_ = time.perf_counter()
+            for _ in range(calls):
+                call(v)
+            torch.cuda.synchronize()
+            times[v].append((time.perf_counter() - t0_) / calls)
+    med = {v: sorted(x)[len(x) // 2] for v, x in times.items()}
+    sp.timing_reset()
+    sp.timing_enable(True)
+    try:
+        for _ in range(calls):
+            call("fused")
+        torch.cuda.synchronize()
+        scopes = _scope_medians(sp.timing_json(), {
+            "multi_accumulate_density_fan", "multi_apply_local_fan", "gpu_accumulate_density_fan_batch",
+            "gpu_apply_local_fan_batch"})
+    finally:
+        sp.timing_enable(False)
+    key = idx[:, 0].astype("int64") * (2 * ny + 1) + idx[:, 1]
+    sticks = len(set(key.tolist()))
+    columns = len(set(idx[:, 0].tolist()))
+    R = nx * ny * nz * 8
+    I, S, V = columns * ny * nz * 16, sticks * nz * 16, len(idx) * 16
+    K = V
+    if tau:
+        middle = 3 * ((S + I) + I) + 2 * R
+        model_bytes = {"fused": V + 3 * (K + S) + middle,
+                       "composed": 3 * (2 * V + K) + 3 * (V + S) + middle}
+    else:
+        middle = 4 * ((S + I) + (2 * I + R) + (I + S))
+        model_bytes = {"fused": (V + 3 * K + 4 * S) + middle + (4 * S + 3 * K + V),
+                       "composed": 3 * (2 * V + K) + 4 * (V + S) + middle + 4 * (S + V) + 3 * (3 * V + K)}
+    print(json.dumps({"workload": "plane-wave " + a.op, "fft_dims": list(basis.fft_dims),
+                      "num_values": len(idx), "sticks": sticks, "members": n,
+                      "batch": os.environ.get("SPFFT_BATCH", "1"),
+                      "values_fan_fused": t.values_fan_fused(n),
+                      "rounds": rounds, "calls_per_round": calls,
+                      "median_us": {v: 1e6 * x for v, x in med.items()},
+                      "min_us": {v: 1e6 * min(x) for v, x in times.items()},
+                      "ratio_composed_over_fused": med["composed"] / med["fused"],
+                      "host_scope_median_s": scopes,
+                      "model_bytes": model_bytes,
                       "model_ratio_composed": model_bytes["composed"] / model_bytes["fused"]}),
           flush=True)
 
