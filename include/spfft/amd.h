@@ -398,6 +398,71 @@ SPFFT_EXPORT SpfftError spfft_amd_float_multi_transform_apply_local_fan(
 SPFFT_EXPORT SpfftError spfft_amd_transform_values_fan_fused(SpfftTransform t, int n, int* fused);
 SPFFT_EXPORT SpfftError spfft_amd_float_transform_values_fan_fused(SpfftFloatTransform t, int n, int* fused);
 
+/* Spinor operators (non-collinear magnetism, spin-orbit coupling). A call takes
+ * nSpinors two-component spinors as 2 * nSpinors transforms on distinct grids,
+ * in the order up_0, dn_0, up_1, dn_1, ... (a transform and its clones). All
+ * must be C2C with equal dimensions, local planes and local element count:
+ * values are matched by position. inputs and outputs hold 2 * nSpinors
+ * pointers in the same order, one interleaved-complex entry per local
+ * frequency value each.
+ *
+ * potential[4] = {v_uu, v_dd, v_ud_re, v_ud_im}: four real arrays over the local
+ * space domain [localZ][dimY][dimX], with v_ud = v_ud_re + i * v_ud_im and
+ * v_du = conj(v_ud). For V * 1 + B . sigma that is v_uu = V + B_z,
+ * v_dd = V - B_z, v_ud_re = B_x, v_ud_im = -B_y.
+ *
+ * Spinor local operator, per spinor s:
+ *   psi_s   = backward_s(in_s)                                     (s = up, dn)
+ *   out_up = scale * forward_up(v_uu * psi_up + v_ud * psi_dn)
+ *   out_dn = scale * forward_dn(conj(v_ud) * psi_up + v_dd * psi_dn)
+ * out == in per member is allowed; inputs are otherwise not modified; the four
+ * potential pointers may repeat.
+ *
+ * Spin density matrix, density[4] = {n_uu, n_dd, n_ud_re, n_ud_im}, four real
+ * arrays over the local space domain:
+ *   n_uu += sum_s w_s |psi_up|^2,  n_dd += sum_s w_s |psi_dn|^2,
+ *   n_ud += sum_s w_s psi_up * conj(psi_dn)        (n_ud = n_ud_re + i * n_ud_im)
+ * The sum runs in list order; the library never zeroes the arrays; weights
+ * holds nSpinors entries. The four arrays must be distinct (equal pointers are
+ * SPFFT_INVALID_PARAMETER_ERROR; partial overlap is undefined). The charge and
+ * magnetisation densities are n = n_uu + n_dd, m_z = n_uu - n_dd,
+ * m_x = 2 * n_ud_re, m_y = -2 * n_ud_im.
+ *
+ * Both calls: the same call on the same data gives the same bits; the space
+ * domains are unspecified afterwards. All arrays are host or device pointers
+ * (weights and the pointer arrays are host arrays).
+ *
+ * Identical plans on one GPU with fused x stages, device pointers and x lines
+ * that fit a workgroup's LDS twice (spfft_amd_transform_spinor_fused) run the
+ * batched z and y launches over all members around one x kernel whose
+ * workgroups hold both components' rows of a tile in LDS (SPFFT_BATCH), at
+ * most 4 spinors per launch: more run in groups of 4 in list order. Everything
+ * else (host transforms, host pointers, distributed grids, long x lines) runs
+ * per spinor in list order: backward of both members, one pass over the two
+ * space domains, and for the operator forward of both; collective per
+ * transform in list order on distributed grids. nSpinors == 0 is a no-op. An
+ * R2C member, a repeated grid, unequal transforms, a null pointer array or
+ * weights with nSpinors > 0, a null input or output with local values, a null
+ * potential or density entry with local planes, equal density pointers or a
+ * bad scaling is SPFFT_INVALID_PARAMETER_ERROR; the transforms stay usable
+ * after an error. */
+SPFFT_EXPORT SpfftError spfft_amd_multi_transform_apply_local_spinor(
+    int nSpinors, SpfftTransform* transforms, const double* const* inputs,
+    const double* const* potential /*4*/, double* const* outputs, SpfftScalingType scaling);
+SPFFT_EXPORT SpfftError spfft_amd_float_multi_transform_apply_local_spinor(
+    int nSpinors, SpfftFloatTransform* transforms, const float* const* inputs,
+    const float* const* potential /*4*/, float* const* outputs, SpfftScalingType scaling);
+SPFFT_EXPORT SpfftError spfft_amd_multi_transform_accumulate_spin_density(
+    int nSpinors, SpfftTransform* transforms, const double* const* inputs, const double* weights,
+    double* const* density /*4*/);
+SPFFT_EXPORT SpfftError spfft_amd_float_multi_transform_accumulate_spin_density(
+    int nSpinors, SpfftFloatTransform* transforms, const float* const* inputs, const float* weights,
+    float* const* density /*4*/);
+/* *fused = 1 if t and a clone of it, called with device pointers, run the fused
+ * spinor x kernels of the two calls above, else 0. */
+SPFFT_EXPORT SpfftError spfft_amd_transform_spinor_fused(SpfftTransform t, int* fused);
+SPFFT_EXPORT SpfftError spfft_amd_float_transform_spinor_fused(SpfftFloatTransform t, int* fused);
+
 /* Timer tree (SPFFT_TIMING=1 or spfft_amd_timing_enable). enable: 0 off, 1 host
  * scopes only (like the reference's timer), 2 host scopes and GPU stage times
  * (a hipEvent per stage boundary, nodes gpu/<direction>/<stage>). */

@@ -20,7 +20,8 @@ from .types import *  # noqa: F401,F403  (exception classes)
 from .grid import (Grid, GridFloat, Transform, TransformFloat,  # noqa: F401
                    multi_transform_accumulate_density, multi_transform_accumulate_density_fan,
                    multi_transform_accumulate_fock, multi_transform_apply_local_fan,
-                   multi_transform_apply_local,
+                   multi_transform_apply_local, multi_transform_apply_local_spinor,
+                   multi_transform_accumulate_spin_density,
                    multi_transform_backward, multi_transform_forward,
                    multi_transform_reciprocal_fan_in, multi_transform_reciprocal_fan_out)
 from .utils.timing import timing_enable, timing_json, timing_report, timing_reset  # noqa: F401

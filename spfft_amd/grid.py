@@ -554,6 +554,19 @@ class _TransformBase:
         _check(self._prec.amd_fn("transform_reciprocal_fan_fused")(self._h, int(n), ctypes.byref(v)))
         return bool(v.value)
 
+    @property
+    def spinor_fused(self) -> bool:
+        """True if this transform and a clone of it, called with device arrays, run the
+        fused spinor x kernels of multi_transform_apply_local_spinor /
+        multi_transform_accumulate_spin_density (C2C plans on one GPU without exchange,
+        fused x stages, x lines that fit a workgroup's LDS twice, SPFFT_BATCH on)."""
+        c = self._cache.get("spinor_fused")
+        if c is None:
+            v = ctypes.c_int()
+            _check(self._prec.amd_fn("transform_spinor_fused")(self._h, ctypes.byref(v)))
+            c = self._cache["spinor_fused"] = bool(v.value)
+        return c
+
     def values_fan_fused(self, n: int) -> bool:
         """True if this transform and n - 1 clones of it, called with device arrays, run the
         fused z fan kernels of multi_transform_accumulate_density_fan /
@@ -1061,3 +1074,111 @@ def multi_transform_apply_local_fan(transforms, values, kernels_in, potentials, 
     for t in transforms:
         t._step_keep = (keeps, ikeep, okeep)
     return output
+
+
+def _four_arrays(x, prec, shape, what, ptr_fn):
+    """Pointer array and keepalives of the four real space-domain arrays of a spinor call:
+    a real [4, z, y, x] array or tensor, or a sequence of four arrays of `shape`."""
+    if _is_torch(x) or isinstance(x, np.ndarray):
+        if x.ndim != 4 or x.shape[0] != 4:
+            raise ValueError(f"{what}: expected shape (4, {', '.join(str(d) for d in shape)}), "
+                             f"got {tuple(x.shape)}")
+        if not (x.is_contiguous() if _is_torch(x) else x.flags.c_contiguous):
+            raise ValueError(f"{what} must be contiguous")
+        parts = [x[k] for k in range(4)]
+    else:
+        parts = list(x)
+        if len(parts) != 4:
+            raise ValueError(f"{what}: expected four arrays, got {len(parts)}")
+    ptrs, keeps = (ctypes.c_void_p * 4)(), []
+    for k in range(4):
+        ptrs[k], keep = ptr_fn(parts[k], prec, shape)
+        keeps.append(keep)
+    return ptrs, keeps
+
+
+def _spinor_common(transforms, inputs, what):
+    n, prec, arr = _multi(transforms)
+    if n % 2:
+        raise ValueError(f"{what}: two transforms (up, down) per spinor")
+    if len(inputs) != n:
+        raise ValueError(f"{what}: one input per transform")
+    if any(t._single != prec.single for t in transforms):
+        raise TypeError("transforms of one call share one precision")
+    shape = transforms[0].space_domain_shape() if n else None
+    if any(tuple(t.space_domain_shape()) != tuple(shape) for t in transforms):
+        raise ValueError("transforms of one call share one space domain shape")
+    iptrs, keeps = (ctypes.c_void_p * max(1, n))(), []
+    for i in range(n):
+        iptrs[i], k = _data_ptr(inputs[i], prec, False, "values")
+        keeps.append(k)
+    return n, prec, arr, shape, iptrs, keeps
+
+
+def multi_transform_apply_local_spinor(transforms, inputs, potential, outputs=None, scaling=Scaling.NONE):
+    """The 2x2 Hermitian local potential applied to two-component spinors in one call.
+
+    `transforms` holds two C2C transforms per spinor on distinct grids (a transform and
+    its clones), in the order up_0, dn_0, up_1, dn_1, ...; `inputs` and `outputs` one array
+    of frequency values per transform in that order. `potential` is a contiguous real
+    [4, z, y, x] array or tensor, or a sequence of four arrays of space_domain_shape():
+    (v_uu, v_dd, v_ud_re, v_ud_im) with v_ud = v_ud_re + i v_ud_im and v_du = conj(v_ud);
+    for V * 1 + B . sigma that is v_uu = V + B_z, v_dd = V - B_z, v_ud_re = B_x,
+    v_ud_im = -B_y. Per spinor, with psi = backward(input):
+
+        out_up = forward_up(v_uu * psi_up + v_ud * psi_dn, scaling)
+        out_dn = forward_dn(conj(v_ud) * psi_up + v_dd * psi_dn, scaling)
+
+    An output may be its input; inputs are otherwise not modified. Identical fused plans on
+    one GPU (see Transform.spinor_fused) with device arrays run one x kernel that holds both
+    components of a tile in LDS between the batched z and y launches. Returns the outputs."""
+    n, prec, arr, shape, iptrs, keeps = _spinor_common(transforms, inputs, "apply_local_spinor")
+    if Scaling(scaling) not in (Scaling.NONE, Scaling.FULL):
+        raise ValueError(f"scaling: expected Scaling.NONE or Scaling.FULL, got {scaling}")
+    fn = prec.amd_fn("multi_transform_apply_local_spinor")
+    if n == 0:
+        _check(fn(0, arr, None, None, None, int(scaling)))
+        return [] if outputs is None else outputs
+    if outputs is None:
+        outputs = [t._default_output() for t in transforms]
+    if len(outputs) != n:
+        raise ValueError("apply_local_spinor: one output per transform")
+    vptrs, vkeeps = _four_arrays(potential, prec, shape, "potential", _potential_ptr)
+    optrs = (ctypes.c_void_p * n)()
+    for i in range(n):
+        optrs[i], k = _data_ptr(outputs[i], prec, True, "output")
+        keeps.append(k)
+    _check(fn(n // 2, arr, iptrs, vptrs, optrs, int(scaling)))
+    # asynchronous execution (set_stream(..., synchronous=False)) may still use them
+    for t in transforms:
+        t._step_keep = (keeps, vkeeps)
+    return outputs
+
+
+def multi_transform_accumulate_spin_density(transforms, inputs, weights, density):
+    """The spin density matrix of two-component spinors, accumulated in one call.
+
+    `transforms` and `inputs` are as in multi_transform_apply_local_spinor; `weights` holds
+    one weight per spinor. `density` is a contiguous real [4, z, y, x] array or tensor, or a
+    sequence of four distinct arrays of space_domain_shape(): (n_uu, n_dd, n_ud_re,
+    n_ud_im), updated in place and never zeroed:
+
+        n_uu += sum_s w_s |psi_up|^2,  n_dd += sum_s w_s |psi_dn|^2,
+        n_ud += sum_s w_s psi_up * conj(psi_dn)
+
+    in list order (the same call on the same data gives the same bits). The charge and
+    magnetisation densities are n = n_uu + n_dd, m_z = n_uu - n_dd, m_x = 2 n_ud_re,
+    m_y = -2 n_ud_im. Returns `density`."""
+    n, prec, arr, shape, iptrs, keeps = _spinor_common(transforms, inputs, "accumulate_spin_density")
+    if 2 * len(weights) != n:
+        raise ValueError("accumulate_spin_density: one weight per spinor")
+    fn = prec.amd_fn("multi_transform_accumulate_spin_density")
+    if n == 0:
+        _check(fn(0, arr, None, None, None))
+        return density
+    rptrs, rkeeps = _four_arrays(density, prec, shape, "density", _density_ptr)
+    ws = ((ctypes.c_float if prec.single else ctypes.c_double) * (n // 2))(*[float(w) for w in weights])
+    _check(fn(n // 2, arr, iptrs, ctypes.cast(ws, ctypes.c_void_p), rptrs))
+    for t in transforms:
+        t._step_keep = (keeps, rkeeps)
+    return density

@@ -458,6 +458,103 @@ class PlaneWaveModel:
             out.append(h)
         return out
 
+    # spinors per multi_transform_*_spinor call (the library's launches take up to 4)
+    SPINOR_GROUP = 4
+
+    def _four_fields(self, v4):
+        """(v_uu, v_dd, v_ud_re, v_ud_im) as one contiguous [4, z, y, x] array of the
+        transforms' precision, where it is."""
+        real = self.transforms[0]._prec
+        if hasattr(v4, "mul_"):
+            return v4.to(real.torch_real).contiguous()
+        if isinstance(v4, np.ndarray):
+            return np.ascontiguousarray(v4, dtype=real.real)
+        parts = [self._real_field(v) for v in v4]
+        if hasattr(parts[0], "mul_"):
+            import torch
+            return torch.stack(parts).contiguous()
+        return np.ascontiguousarray(np.stack(parts))
+
+    def apply_spinor_potential(self, spinors: Sequence, v4, unfused: bool = False) -> List:
+        """The 2x2 Hermitian local potential on two-component spinors (non-collinear
+        magnetism, spin-orbit coupling): for every spinor (c_up, c_dn) the coefficients of
+        v_uu psi_up + v_ud psi_dn and conj(v_ud) psi_up + v_dd psi_dn, as a list of pairs.
+        `v4` holds (v_uu, v_dd, v_ud_re, v_ud_im) [4][z][y][x]; for V + B . sigma:
+        v_uu = V + B_z, v_dd = V - B_z, v_ud_re = B_x, v_ud_im = -B_y.
+
+        One multi_transform_apply_local_spinor call per group of 4 spinors on wavefunction
+        transforms (on the GPU the x stage holds both components of a tile in LDS and mixes
+        them there; the space domains are never formed); `unfused` runs the composition
+        multi_transform_backward of both components, the mix as array passes over the two
+        space domains, multi_transform_forward."""
+        from ..grid import (multi_transform_apply_local_spinor, multi_transform_backward,
+                            multi_transform_forward)
+        spinors = [tuple(s) for s in spinors]
+        v = self._four_fields(v4)
+        out = []
+        if unfused:
+            vud = v[2] + 1j * v[3]
+            vdu = vud.conj() if hasattr(vud, "conj") else np.conj(vud)
+        for start in range(0, len(spinors), self.SPINOR_GROUP):
+            group = spinors[start:start + self.SPINOR_GROUP]
+            ts = self._wave_transforms(2 * len(group))
+            flat = [c for s in group for c in s]
+            if not unfused:
+                res = multi_transform_apply_local_spinor(ts, flat, v, scaling=Scaling.FULL)
+            else:
+                spaces = multi_transform_backward(ts, flat)
+                for u, d in zip(spaces[0::2], spaces[1::2]):
+                    nu = v[0] * u + vud * d
+                    nd = vdu * u + v[1] * d
+                    if hasattr(u, "copy_"):
+                        u.copy_(nu)
+                        d.copy_(nd)
+                    else:
+                        u[...] = nu
+                        d[...] = nd
+                res = multi_transform_forward(ts, scalings=[Scaling.FULL] * len(ts))
+            res = [self._copy(r) for r in res]
+            out.extend(zip(res[0::2], res[1::2]))
+        return out
+
+    def spin_density(self, spinors: Sequence, weights: Sequence[float], unfused: bool = False):
+        """(n, m_x, m_y, m_z)(r) = sum_s w_s psi_s^+ (1, sigma) psi_s of two-component
+        spinors (c_up, c_dn) on the real-space grid [z][y][x], as four new real arrays of the
+        transforms' precision where the transforms run.
+
+        One multi_transform_accumulate_spin_density call per group of 4 spinors into the
+        zeroed spin density matrix (n_uu, n_dd, n_ud_re, n_ud_im), from which n = n_uu +
+        n_dd, m_z = n_uu - n_dd, m_x = 2 n_ud_re, m_y = -2 n_ud_im (on the GPU the x stage
+        updates its rows of the four arrays from LDS); `unfused` runs the composition
+        multi_transform_backward and array passes over the two space domains."""
+        from ..grid import multi_transform_accumulate_spin_density, multi_transform_backward
+        spinors, weights = [tuple(s) for s in spinors], [float(w) for w in weights]
+        t0 = self.transforms[0]
+        shape = (4,) + tuple(t0.space_domain_shape())
+        if self.pu == ProcessingUnit.GPU:
+            import torch
+            first = spinors[0][0] if spinors else None
+            dev = first.device if getattr(first, "is_cuda", False) else "cuda"
+            m = torch.zeros(shape, dtype=t0._prec.torch_real, device=dev)
+        else:
+            m = np.zeros(shape, dtype=t0._prec.real)
+        for start in range(0, len(spinors), self.SPINOR_GROUP):
+            group = spinors[start:start + self.SPINOR_GROUP]
+            ws = weights[start:start + self.SPINOR_GROUP]
+            ts = self._wave_transforms(2 * len(group))
+            flat = [c for s in group for c in s]
+            if not unfused:
+                multi_transform_accumulate_spin_density(ts, flat, ws, m)
+                continue
+            spaces = multi_transform_backward(ts, flat)
+            for u, d, w in zip(spaces[0::2], spaces[1::2], ws):
+                ud = u * (d.conj() if hasattr(d, "conj") else np.conj(d))
+                m[0] += w * (u.real ** 2 + u.imag ** 2)
+                m[1] += w * (d.real ** 2 + d.imag ** 2)
+                m[2] += w * ud.real
+                m[3] += w * ud.imag
+        return m[0] + m[1], 2 * m[2], -2 * m[3], m[0] - m[1]
+
     def kinetic(self, psi: Sequence) -> List:
         """T psi_b = |G|^2/2 c_G (diagonal in the plane-wave basis)."""
         g2 = self.basis.g2

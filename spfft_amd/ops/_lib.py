@@ -144,6 +144,10 @@ def _prototypes(lib):
         sig[pre + "multi_transform_apply_local_fan"] = [I, c_void_pp, D, c_void_pp, c_void_pp, c_void_pp,
                                                         I, D, I]
         sig[pre + "transform_values_fan_fused"] = [V, I, c_int_p]
+    for pre in ("spfft_amd_", "spfft_amd_float_"):
+        sig[pre + "multi_transform_apply_local_spinor"] = [I, c_void_pp, c_void_pp, c_void_pp, c_void_pp, I]
+        sig[pre + "multi_transform_accumulate_spin_density"] = [I, c_void_pp, c_void_pp, D, c_void_pp]
+        sig[pre + "transform_spinor_fused"] = [V, c_int_p]
     sig["spfft_amd_timing_enable"] = [I]
     sig["spfft_amd_timing_reset"] = []
     sig["spfft_amd_timing_json"] = [ctypes.c_char_p, ctypes.c_size_t, c_size_t_p]

@@ -73,6 +73,16 @@ void multi_apply_local_fan_handles(int n, Transform** ts, const double* input, c
 void multi_apply_local_fan_handles(int n, TransformFloat** ts, const float* input, const float* const* kernelsIn,
                                    const float* const* potentials, const float* const* kernelsOut,
                                    bool complexKernel, float* output, SpfftScalingType scaling);
+void multi_apply_local_spinor_handles(int nSpinors, Transform** ts, const double* const* inputs,
+                                       const double* const* potential, double* const* outputs,
+                                       SpfftScalingType scaling);
+void multi_apply_local_spinor_handles(int nSpinors, TransformFloat** ts, const float* const* inputs,
+                                       const float* const* potential, float* const* outputs,
+                                       SpfftScalingType scaling);
+void multi_accumulate_spin_density_handles(int nSpinors, Transform** ts, const double* const* inputs,
+                                            const double* weights, double* const* density);
+void multi_accumulate_spin_density_handles(int nSpinors, TransformFloat** ts, const float* const* inputs,
+                                            const float* weights, float* const* density);
 }  // namespace spfft
 
 using namespace spfft;
@@ -832,6 +842,63 @@ SpfftError spfft_amd_float_transform_values_fan_fused(SpfftFloatTransform t, int
   if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
   return with_handle<TransformFloat>(
       t, [&](TransformFloat& x) { *fused = x.impl()->values_fan_fused(n) ? 1 : 0; });
+}
+
+SpfftError spfft_amd_multi_transform_apply_local_spinor(int nSpinors, SpfftTransform* transforms,
+                                                        const double* const* inputs,
+                                                        const double* const* potential,
+                                                        double* const* outputs, SpfftScalingType scaling) {
+  if (nSpinors < 0 || (nSpinors > 0 && !transforms)) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < 2 * nSpinors; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_apply_local_spinor_handles(nSpinors, reinterpret_cast<Transform**>(transforms), inputs, potential,
+                                     outputs, scaling);
+  });
+}
+SpfftError spfft_amd_float_multi_transform_apply_local_spinor(int nSpinors, SpfftFloatTransform* transforms,
+                                                              const float* const* inputs,
+                                                              const float* const* potential,
+                                                              float* const* outputs, SpfftScalingType scaling) {
+  if (nSpinors < 0 || (nSpinors > 0 && !transforms)) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < 2 * nSpinors; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_apply_local_spinor_handles(nSpinors, reinterpret_cast<TransformFloat**>(transforms), inputs, potential,
+                                     outputs, scaling);
+  });
+}
+SpfftError spfft_amd_multi_transform_accumulate_spin_density(int nSpinors, SpfftTransform* transforms,
+                                                             const double* const* inputs,
+                                                             const double* weights, double* const* density) {
+  if (nSpinors < 0 || (nSpinors > 0 && !transforms)) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < 2 * nSpinors; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_accumulate_spin_density_handles(nSpinors, reinterpret_cast<Transform**>(transforms), inputs, weights,
+                                          density);
+  });
+}
+SpfftError spfft_amd_float_multi_transform_accumulate_spin_density(int nSpinors,
+                                                                   SpfftFloatTransform* transforms,
+                                                                   const float* const* inputs,
+                                                                   const float* weights,
+                                                                   float* const* density) {
+  if (nSpinors < 0 || (nSpinors > 0 && !transforms)) return SPFFT_INVALID_PARAMETER_ERROR;
+  for (int i = 0; i < 2 * nSpinors; ++i)
+    if (!transforms[i]) return SPFFT_INVALID_HANDLE_ERROR;
+  return guarded([&] {
+    multi_accumulate_spin_density_handles(nSpinors, reinterpret_cast<TransformFloat**>(transforms), inputs,
+                                          weights, density);
+  });
+}
+SpfftError spfft_amd_transform_spinor_fused(SpfftTransform t, int* fused) {
+  if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
+  return with_handle<Transform>(t, [&](Transform& x) { *fused = x.impl()->spinor_fused() ? 1 : 0; });
+}
+SpfftError spfft_amd_float_transform_spinor_fused(SpfftFloatTransform t, int* fused) {
+  if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
+  return with_handle<TransformFloat>(t, [&](TransformFloat& x) { *fused = x.impl()->spinor_fused() ? 1 : 0; });
 }
 
 SpfftError spfft_amd_timing_enable(int enable) {

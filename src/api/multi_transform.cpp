@@ -732,6 +732,197 @@ void multi_apply_local_fan(const std::vector<TransformImpl<T>*>& ts, const T* in
   std::copy(sum.begin(), sum.begin() + 2 * count, output);
 }
 
+// ------------------------------------------------------------ spinor operators
+// The checks both spinor calls share over the 2S members {up_0, dn_0, ...};
+// returns whether the fused x stages run: GPU transforms with spinor_fused
+// plans and equal keys. The arrays are checked by the callers.
+template <typename T>
+bool check_spinors(const std::vector<TransformImpl<T>*>& ts) {
+  check_distinct_grids(ts);
+  const int n = static_cast<int>(ts.size());
+  for (int i = 0; i < n; ++i) {
+    const IndexPlan& p = ts[i]->plan();
+    const IndexPlan& p0 = ts[0]->plan();
+    // a real space domain cannot hold the off-diagonal term
+    if (p.type != SPFFT_TRANS_C2C) throw InvalidParameterError();
+    // values are matched by position, space domains by element
+    if (p.dimX != p0.dimX || p.dimY != p0.dimY || p.dimZ != p0.dimZ || p.local_planes() != p0.local_planes() ||
+        p.numLocalElements != p0.numLocalElements)
+      throw InvalidParameterError();
+  }
+  for (int i = 0; i < n; ++i) {
+    if (!ts[i]->is_gpu()) return false;
+    ts[i]->gpu()->ensure_stream();
+    if (!ts[i]->gpu()->spinor_fused() || ts[i]->gpu()->batch_key() != ts[0]->gpu()->batch_key()) return false;
+  }
+  return n > 0;
+}
+
+// Both members' backward results in host memory (host transforms, or a host
+// and a GPU member): the space domains the host loops below work on.
+template <typename T>
+void spinor_host_backward(TransformImpl<T>* up, TransformImpl<T>* dn, const T* inUp, const T* inDn, T*& su,
+                          T*& sd) {
+  up->backward(inUp, SPFFT_PU_HOST);
+  dn->backward(inDn, SPFFT_PU_HOST);
+  up->synchronize();
+  dn->synchronize();
+  su = up->space_domain_data(SPFFT_PU_HOST);
+  sd = dn->space_domain_data(SPFFT_PU_HOST);
+}
+
+// out_up = scale forward_up(v_uu psi_up + v_ud psi_dn), out_dn = scale
+// forward_dn(conj(v_ud) psi_up + v_dd psi_dn) per spinor, psi = backward(in).
+// Fused plans with device arrays run GpuExecutor::apply_local_spinor_batch in
+// groups of dev::kMaxSpinors spinors in list order; everything else the
+// composition per spinor in list order: backward of both members into their
+// space domains, the 2x2 mix of the two space domains (a kernel on the up
+// member's stream, or a loop on the host), forward of both.
+template <typename T>
+void multi_apply_local_spinor(const std::vector<TransformImpl<T>*>& ts, const T* const* inputs,
+                              const T* const* potential, T* const* outputs, SpfftScalingType scaling) {
+  SPFFT_TIMED_SCOPE("multi_apply_local_spinor");
+  bool fused = check_spinors<T>(ts);
+  if (scaling != SPFFT_NO_SCALING && scaling != SPFFT_FULL_SCALING) throw InvalidParameterError();
+  const int n = static_cast<int>(ts.size());
+  if (n == 0) return;
+  if (!inputs || !potential || !outputs) throw InvalidParameterError();
+  const IndexPlan& p0 = ts[0]->plan();
+  const std::size_t count = static_cast<std::size_t>(p0.numLocalElements);
+  const std::size_t space = static_cast<std::size_t>(p0.local_planes()) * p0.dimY * p0.dimX;
+  for (int k = 0; k < 4; ++k) {
+    if (space > 0 && !potential[k]) throw InvalidParameterError();
+    if (space > 0 && !is_device_pointer(potential[k])) fused = false;
+  }
+  for (int i = 0; i < n; ++i) {
+    if (count > 0 && (!inputs[i] || !outputs[i])) throw InvalidParameterError();
+    if (count > 0 && (!is_device_pointer(inputs[i]) || !is_device_pointer(outputs[i]))) fused = false;
+  }
+  if (fused) {
+    for (int i = 0; i < n; i += 2 * dev::kMaxSpinors) {
+      const int e = std::min(n, i + 2 * dev::kMaxSpinors);
+      std::vector<GpuExecutor<T>*> ex;
+      std::vector<const T*> ins;
+      std::vector<T*> outs;
+      for (int j = i; j < e; ++j) {
+        ex.push_back(ts[j]->gpu());
+        ins.push_back(inputs[j]);
+        outs.push_back(outputs[j]);
+      }
+      GpuExecutor<T>::apply_local_spinor_batch(ex, ins, potential, outs, scaling);
+    }
+    for (int i = 0; i < n; ++i)
+      if (ts[i]->gpu()->synchronous()) ts[i]->synchronize();
+    return;
+  }
+  for (int i = 0; i < n; i += 2) {
+    TransformImpl<T>* up = ts[i];
+    TransformImpl<T>* dn = ts[i + 1];
+    if (up->is_gpu() && dn->is_gpu()) {
+      up->backward(inputs[i], SPFFT_PU_GPU);
+      dn->backward(inputs[i + 1], SPFFT_PU_GPU);
+      up->gpu()->spinor_mix_space(dn->gpu(), potential);
+      up->forward(SPFFT_PU_GPU, outputs[i], scaling);
+      dn->forward(SPFFT_PU_GPU, outputs[i + 1], scaling);
+      // the staged potential and the space domains are free for the next spinor
+      up->synchronize();
+      dn->synchronize();
+      continue;
+    }
+    for (int k = 0; k < 4; ++k)
+      if (space > 0 && is_device_pointer(potential[k])) throw InvalidParameterError();
+    T *su = nullptr, *sd = nullptr;
+    spinor_host_backward<T>(up, dn, inputs[i], inputs[i + 1], su, sd);
+    for (std::size_t r = 0; r < space; ++r) {
+      const T vuu = potential[0][r], vdd = potential[1][r], vre = potential[2][r], vim = potential[3][r];
+      const T ux = su[2 * r], uy = su[2 * r + 1], dx = sd[2 * r], dy = sd[2 * r + 1];
+      su[2 * r] = vuu * ux + (vre * dx - vim * dy);
+      su[2 * r + 1] = vuu * uy + (vre * dy + vim * dx);
+      sd[2 * r] = vdd * dx + (vre * ux + vim * uy);
+      sd[2 * r + 1] = vdd * dy + (vre * uy - vim * ux);
+    }
+    up->forward(SPFFT_PU_HOST, outputs[i], scaling);
+    dn->forward(SPFFT_PU_HOST, outputs[i + 1], scaling);
+    up->synchronize();
+    dn->synchronize();
+  }
+}
+
+// n_uu += sum_s w_s |psi_up|^2, n_dd += sum_s w_s |psi_dn|^2, n_ud += sum_s w_s
+// psi_up conj(psi_dn), in list order. Fused plans with device arrays run
+// GpuExecutor::accumulate_spin_density_batch in groups of dev::kMaxSpinors
+// spinors, one group behind the other on the leaders' streams; everything else
+// per spinor in list order: backward of both members, then one pass over the
+// two space domains (a kernel on the up member's stream, or a loop on the
+// host), each update behind the previous one.
+template <typename T>
+void multi_accumulate_spin_density(const std::vector<TransformImpl<T>*>& ts, const T* const* inputs,
+                                   const T* weights, T* const* density) {
+  SPFFT_TIMED_SCOPE("multi_accumulate_spin_density");
+  bool fused = check_spinors<T>(ts);
+  const int n = static_cast<int>(ts.size());
+  if (n == 0) return;
+  if (!inputs || !weights || !density) throw InvalidParameterError();
+  const IndexPlan& p0 = ts[0]->plan();
+  const std::size_t count = static_cast<std::size_t>(p0.numLocalElements);
+  const std::size_t space = static_cast<std::size_t>(p0.local_planes()) * p0.dimY * p0.dimX;
+  for (int k = 0; k < 4; ++k) {
+    if (space > 0 && !density[k]) throw InvalidParameterError();
+    for (int j = 0; j < k; ++j)
+      if (space > 0 && density[k] == density[j]) throw InvalidParameterError();
+    if (space > 0 && !is_device_pointer(density[k])) fused = false;
+  }
+  for (int i = 0; i < n; ++i) {
+    if (count > 0 && !inputs[i]) throw InvalidParameterError();
+    if (count > 0 && !is_device_pointer(inputs[i])) fused = false;
+  }
+  if (fused) {
+    GpuExecutor<T>* prev = nullptr;
+    for (int i = 0; i < n; i += 2 * dev::kMaxSpinors) {
+      const int e = std::min(n, i + 2 * dev::kMaxSpinors);
+      std::vector<GpuExecutor<T>*> ex;
+      std::vector<const T*> ins;
+      std::vector<T> ws;
+      for (int j = i; j < e; ++j) {
+        ex.push_back(ts[j]->gpu());
+        ins.push_back(inputs[j]);
+        if ((j - i) % 2 == 0) ws.push_back(weights[j / 2]);
+      }
+      // a group's update of the arrays comes behind the previous group's
+      GpuExecutor<T>::accumulate_spin_density_batch(ex, ins, ws, density, prev);
+      prev = ex[0];
+    }
+    for (int i = 0; i < n; ++i)
+      if (ts[i]->gpu()->synchronous()) ts[i]->synchronize();
+    return;
+  }
+  for (int i = 0; i < n; i += 2) {
+    TransformImpl<T>* up = ts[i];
+    TransformImpl<T>* dn = ts[i + 1];
+    const T w = weights[i / 2];
+    if (up->is_gpu() && dn->is_gpu()) {
+      up->backward(inputs[i], SPFFT_PU_GPU);
+      dn->backward(inputs[i + 1], SPFFT_PU_GPU);
+      up->gpu()->spin_density_space(dn->gpu(), density, w);
+      // the next spinor's update of the arrays comes behind this one
+      up->synchronize();
+      dn->synchronize();
+      continue;
+    }
+    for (int k = 0; k < 4; ++k)
+      if (space > 0 && is_device_pointer(density[k])) throw InvalidParameterError();
+    T *su = nullptr, *sd = nullptr;
+    spinor_host_backward<T>(up, dn, inputs[i], inputs[i + 1], su, sd);
+    for (std::size_t r = 0; r < space; ++r) {
+      const T ux = su[2 * r], uy = su[2 * r + 1], dx = sd[2 * r], dy = sd[2 * r + 1];
+      density[0][r] += w * (ux * ux + uy * uy);
+      density[1][r] += w * (dx * dx + dy * dy);
+      density[2][r] += w * (ux * dx + uy * dy);
+      density[3][r] += w * (uy * dx - ux * dy);
+    }
+  }
+}
+
 template <typename TR, typename T>
 std::vector<TransformImpl<T>*> impls(int n, TR* transforms) {
   if (n < 0 || (n > 0 && !transforms)) throw InvalidParameterError();
@@ -889,6 +1080,36 @@ void multi_apply_local_fan_handles(int n, TransformFloat** ts, const float* inpu
   std::vector<TransformImpl<float>*> v;
   for (int i = 0; i < n; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
   multi_apply_local_fan<float>(v, input, kernelsIn, potentials, kernelsOut, complexKernel, output, scaling);
+}
+void multi_apply_local_spinor_handles(int nSpinors, Transform** ts, const double* const* inputs,
+                                       const double* const* potential, double* const* outputs,
+                                       SpfftScalingType scaling) {
+  if (nSpinors < 0 || (nSpinors > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<double>*> v;
+  for (int i = 0; i < 2 * nSpinors; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_apply_local_spinor<double>(v, inputs, potential, outputs, scaling);
+}
+void multi_apply_local_spinor_handles(int nSpinors, TransformFloat** ts, const float* const* inputs,
+                                       const float* const* potential, float* const* outputs,
+                                       SpfftScalingType scaling) {
+  if (nSpinors < 0 || (nSpinors > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<float>*> v;
+  for (int i = 0; i < 2 * nSpinors; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_apply_local_spinor<float>(v, inputs, potential, outputs, scaling);
+}
+void multi_accumulate_spin_density_handles(int nSpinors, Transform** ts, const double* const* inputs,
+                                            const double* weights, double* const* density) {
+  if (nSpinors < 0 || (nSpinors > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<double>*> v;
+  for (int i = 0; i < 2 * nSpinors; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_accumulate_spin_density<double>(v, inputs, weights, density);
+}
+void multi_accumulate_spin_density_handles(int nSpinors, TransformFloat** ts, const float* const* inputs,
+                                            const float* weights, float* const* density) {
+  if (nSpinors < 0 || (nSpinors > 0 && !ts)) throw InvalidParameterError();
+  std::vector<TransformImpl<float>*> v;
+  for (int i = 0; i < 2 * nSpinors; ++i) v.push_back(ts[i] ? ts[i]->impl().get() : nullptr);
+  multi_accumulate_spin_density<float>(v, inputs, weights, density);
 }
 void multi_forward_handles(int n, TransformFloat** ts, SpfftProcessingUnitType* in, float** out,
                            SpfftScalingType* sc) {

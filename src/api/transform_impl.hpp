@@ -58,6 +58,10 @@ public:
   // run the fused z fan stages of multi_transform_accumulate_density_fan /
   // multi_transform_apply_local_fan
   bool values_fan_fused(int n) const;
+  // whether this transform and a clone of it, called with device pointers, run
+  // the fused x stages of multi_transform_apply_local_spinor /
+  // multi_transform_accumulate_spin_density
+  bool spinor_fused() const { return gpu_ && gpu_->spinor_fused(); }
 
   // Exchange (Fock) pair operator: acc += weight * a * backward(K * (scale *
   // forward(conj(a) * b))) with a, b and acc over the local space domain

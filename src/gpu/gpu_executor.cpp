@@ -2298,6 +2298,199 @@ void GpuExecutor<T>::copy_values(T* dst, const T* src) {
   gpu_check(hipMemcpyAsync(dst, src, sizeof(cx<T>) * count, hipMemcpyDefault, stream_), "hipMemcpyAsync");
 }
 
+// ------------------------------------------------------------ spinor operators
+template <typename T>
+bool GpuExecutor<T>::spinor_fused() const {
+  if (!batchable() || !applyFused_ || !densityFused_) return false;
+  if (spinorFits_ < 0) spinorFits_ = dev::x_spinor_fits<T>(plan_->dimX) ? 1 : 0;
+  return spinorFits_ == 1;
+}
+
+// z backward and y backward of all 2S members in one launch each, the spinor x
+// apply stage on the S pairs of intermediates, y forward and z forward of all
+// members in one launch each.
+template <typename T>
+void GpuExecutor<T>::apply_local_spinor_batch(const std::vector<GpuExecutor*>& ex,
+                                              const std::vector<const T*>& inputs, const T* const* potential,
+                                              const std::vector<T*>& outputs, SpfftScalingType scaling) {
+  SPFFT_TIMED_SCOPE("gpu_apply_local_spinor_batch");
+  const int n = static_cast<int>(ex.size());
+  if (n < 2 || n % 2 != 0 || n > dev::kMaxBatch || inputs.size() != ex.size() || outputs.size() != ex.size() ||
+      !potential)
+    throw InternalError();
+  GpuExecutor* l = ex[0];
+  DeviceGuard guard(l->deviceId_);
+  for (GpuExecutor* e : ex)
+    if (!e->spinor_fused() || e->batchKey_ != l->batchKey_) throw InternalError();
+  const IndexPlan& p = *l->plan_;
+  bool shared = n > 2;  // more than one spinor reads the potential
+  for (int k = 0; k < 4; ++k)
+    if (p.local_planes() > 0 && (!potential[k] || !is_device_pointer(potential[k]))) throw InvalidParameterError();
+  dev::BatchPtrs zb{}, yb{}, yf{}, zf{};
+  zb.count = yb.count = yf.count = zf.count = n;
+  cx<T>* up[dev::kMaxSpinors];
+  cx<T>* dn[dev::kMaxSpinors];
+  for (int i = 0; i < n; ++i) {
+    GpuExecutor* e = ex[i];
+    if (p.numLocalElements > 0 && (!inputs[i] || !is_device_pointer(inputs[i]) || !outputs[i] ||
+                                   !is_device_pointer(outputs[i])))
+      throw InvalidParameterError();
+    void* stick = e->grid_->device_slot(GridImpl<T>::kStickSide);
+    void* slab = e->grid_->device_slot(GridImpl<T>::kSlabSide);
+    void* inter = e->grid_->device_slot(GridImpl<T>::kInter);
+    zb.in[i] = inputs[i];
+    zb.out[i] = stick;
+    yb.in[i] = slab;
+    yb.out[i] = inter;
+    (i % 2 ? dn : up)[i / 2] = static_cast<cx<T>*>(inter);
+    yf.in[i] = inter;
+    yf.out[i] = slab;
+    zf.in[i] = stick;
+    zf.out[i] = outputs[i];
+  }
+  batch_join(ex);
+  auto za = l->zargs();
+  auto ya = l->yargs();
+  auto xa = l->xargs();
+  hipStream_t s = l->stream_;
+  l->stage_mark("backward", nullptr);
+  za.batch = zb;
+  dev::launch_z_backward<T, cx<T>>(za, static_cast<const cx<T>*>(zb.in[0]), static_cast<cx<T>*>(zb.out[0]),
+                                   l->twZ_->data<cx<T>>(), s);
+  l->stage_mark("backward", "z");
+  ya.batch = yb;
+  dev::launch_y_backward<T, cx<T>>(ya, static_cast<const cx<T>*>(yb.in[0]), static_cast<cx<T>*>(yb.out[0]),
+                                   l->twY_->data<cx<T>>(), s);
+  l->stage_mark("backward", "y");
+  dev::launch_x_spinor_apply<T>(xa, n / 2, up, dn, potential, shared, l->twX_->data<cx<T>>(), s);
+  l->stage_mark("backward", "x_spinor_apply");
+  ya.batch = yf;
+  dev::launch_y_forward<T, cx<T>>(ya, static_cast<const cx<T>*>(yf.in[0]), static_cast<cx<T>*>(yf.out[0]),
+                                  l->twY_->data<cx<T>>(), s);
+  l->stage_mark("backward", "y");
+  za.batch = zf;
+  dev::launch_z_forward<T, cx<T>>(za, static_cast<const cx<T>*>(zf.in[0]), static_cast<cx<T>*>(zf.out[0]),
+                                  full_scale_factor<T>(p, scaling), l->twZ_->data<cx<T>>(), s);
+  l->stage_mark("backward", "z");
+  batch_release(ex);
+}
+
+// z backward and y backward of all 2S members in one launch each, then one
+// spinor x density launch whose workgroups loop over the spinors for their
+// tile of the four arrays.
+template <typename T>
+void GpuExecutor<T>::accumulate_spin_density_batch(const std::vector<GpuExecutor*>& ex,
+                                                   const std::vector<const T*>& inputs,
+                                                   const std::vector<T>& weights, T* const* density,
+                                                   GpuExecutor* after) {
+  SPFFT_TIMED_SCOPE("gpu_accumulate_spin_density_batch");
+  const int n = static_cast<int>(ex.size());
+  if (n < 2 || n % 2 != 0 || n > dev::kMaxBatch || inputs.size() != ex.size() ||
+      weights.size() * 2 != ex.size() || !density)
+    throw InternalError();
+  GpuExecutor* l = ex[0];
+  DeviceGuard guard(l->deviceId_);
+  for (GpuExecutor* e : ex)
+    if (!e->spinor_fused() || e->batchKey_ != l->batchKey_) throw InternalError();
+  const IndexPlan& p = *l->plan_;
+  for (int k = 0; k < 4; ++k)
+    if (p.local_planes() > 0 && (!density[k] || !is_device_pointer(density[k]))) throw InvalidParameterError();
+  dev::BatchPtrs zb{}, yb{};
+  zb.count = yb.count = n;
+  const cx<T>* up[dev::kMaxSpinors];
+  const cx<T>* dn[dev::kMaxSpinors];
+  for (int i = 0; i < n; ++i) {
+    GpuExecutor* e = ex[i];
+    if (p.numLocalElements > 0 && (!inputs[i] || !is_device_pointer(inputs[i]))) throw InvalidParameterError();
+    zb.in[i] = inputs[i];
+    zb.out[i] = e->grid_->device_slot(GridImpl<T>::kStickSide);
+    yb.in[i] = e->grid_->device_slot(GridImpl<T>::kSlabSide);
+    yb.out[i] = e->grid_->device_slot(GridImpl<T>::kInter);
+    (i % 2 ? dn : up)[i / 2] = static_cast<const cx<T>*>(yb.out[i]);
+  }
+  batch_join(ex);
+  auto za = l->zargs();
+  auto ya = l->yargs();
+  auto xa = l->xargs();
+  hipStream_t s = l->stream_;
+  l->stage_mark("backward", nullptr);
+  za.batch = zb;
+  dev::launch_z_backward<T, cx<T>>(za, static_cast<const cx<T>*>(zb.in[0]), static_cast<cx<T>*>(zb.out[0]),
+                                   l->twZ_->data<cx<T>>(), s);
+  l->stage_mark("backward", "z");
+  ya.batch = yb;
+  dev::launch_y_backward<T, cx<T>>(ya, static_cast<const cx<T>*>(yb.in[0]), static_cast<cx<T>*>(yb.out[0]),
+                                   l->twY_->data<cx<T>>(), s);
+  l->stage_mark("backward", "y");
+  l->order_after_density(after);
+  dev::launch_x_spinor_density<T>(xa, n / 2, up, dn, weights.data(), density, l->twX_->data<cx<T>>(), s);
+  l->stage_mark("backward", "x_spinor_density");
+  batch_release(ex);
+}
+
+template <typename T>
+void GpuExecutor<T>::spinor_mix_space(GpuExecutor* dn, const T* const* potential) {
+  DeviceGuard guard(deviceId_);
+  const std::size_t count = space_elements();
+  if (count == 0) return;
+  const T* pot[4];
+  bool host = false;
+  for (int k = 0; k < 4; ++k) {
+    if (!potential[k]) throw InvalidParameterError();
+    host = host || !is_device_pointer(potential[k]);
+  }
+  order_after_density(dn);  // dn's backward
+  if (host) {
+    if (!spinorBuf_ || spinorBuf_->bytes() < 4 * count * sizeof(T))
+      spinorBuf_.reset(new DeviceBuffer(4 * count * sizeof(T)));
+    for (int k = 0; k < 4; ++k) {
+      T* dst = spinorBuf_->data<T>() + k * count;
+      gpu_check(hipMemcpyAsync(dst, potential[k], count * sizeof(T), hipMemcpyDefault, stream_),
+                "hipMemcpyAsync");
+      pot[k] = dst;
+    }
+  } else {
+    for (int k = 0; k < 4; ++k) pot[k] = potential[k];
+  }
+  dev::launch_space_spinor_mix<T>(static_cast<cx<T>*>(grid_->device_slot(GridImpl<T>::kSpace)),
+                                  static_cast<cx<T>*>(dn->grid_->device_slot(GridImpl<T>::kSpace)), pot,
+                                  static_cast<long long>(count), stream_);
+  dn->order_after_density(this);  // dn's forward reads the mixed space domain
+}
+
+template <typename T>
+void GpuExecutor<T>::spin_density_space(GpuExecutor* dn, T* const* density, T weight) {
+  DeviceGuard guard(deviceId_);
+  const std::size_t count = space_elements();
+  if (count == 0) return;
+  T* arr[4];
+  bool host = false;
+  for (int k = 0; k < 4; ++k) {
+    if (!density[k]) throw InvalidParameterError();
+    host = host || !is_device_pointer(density[k]);
+  }
+  order_after_density(dn);  // dn's backward
+  if (host) {
+    if (!spinorBuf_ || spinorBuf_->bytes() < 4 * count * sizeof(T))
+      spinorBuf_.reset(new DeviceBuffer(4 * count * sizeof(T)));
+    for (int k = 0; k < 4; ++k) {
+      arr[k] = spinorBuf_->data<T>() + k * count;
+      gpu_check(hipMemcpyAsync(arr[k], density[k], count * sizeof(T), hipMemcpyDefault, stream_),
+                "hipMemcpyAsync");
+    }
+  } else {
+    for (int k = 0; k < 4; ++k) arr[k] = density[k];
+  }
+  dev::launch_space_spin_density<T>(static_cast<const cx<T>*>(grid_->device_slot(GridImpl<T>::kSpace)),
+                                    static_cast<const cx<T>*>(dn->grid_->device_slot(GridImpl<T>::kSpace)), arr,
+                                    weight, static_cast<long long>(count), stream_);
+  if (host)
+    for (int k = 0; k < 4; ++k)
+      gpu_check(hipMemcpyAsync(density[k], arr[k], count * sizeof(T), hipMemcpyDefault, stream_),
+                "hipMemcpyAsync");
+  dn->order_after_density(this);  // dn's space domain is free again
+}
+
 template class GpuExecutor<double>;
 template class GpuExecutor<float>;
 

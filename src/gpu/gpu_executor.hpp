@@ -178,6 +178,33 @@ public:
   void values_add(cx<T>* acc, const cx<T>* in);
   void copy_values(T* dst, const T* src);
 
+  // Spinor operators (multi_transform_apply_local_spinor / accumulate_spin_density)
+  // of batchable() C2C plans with fused x stages, equal keys and an x line
+  // region that fits a workgroup's LDS twice (spinor_fused), on the leader's
+  // stream. ex = {up_0, dn_0, up_1, dn_1, ...}, at most dev::kMaxBatch / 2
+  // spinors; every array is a device pointer; `potential` and `density` hold
+  // four real arrays over the local space domain. apply_local_spinor_batch:
+  // the batched z and y backward launches over all members, the spinor x apply
+  // stage (one grid plane per spinor, both components of a tile in LDS), the
+  // batched y and z forward launches. accumulate_spin_density_batch: z and y
+  // backward, then the spinor x density stage whose workgroups loop over the
+  // spinors in order; `after`: the executor whose stream holds the latest
+  // update of the arrays (the previous group of the call). The space domains
+  // are untouched.
+  bool spinor_fused() const;
+  static void apply_local_spinor_batch(const std::vector<GpuExecutor*>& ex, const std::vector<const T*>& inputs,
+                                       const T* const* potential, const std::vector<T*>& outputs,
+                                       SpfftScalingType scaling);
+  static void accumulate_spin_density_batch(const std::vector<GpuExecutor*>& ex,
+                                            const std::vector<const T*>& inputs, const std::vector<T>& weights,
+                                            T* const* density, GpuExecutor* after = nullptr);
+  // Pieces of the composed spinor paths; this executor is the up member, `dn`
+  // the down member, both with their results in the device space domains. The
+  // pass runs on this stream behind dn's work so far, and dn's stream waits
+  // for it. Host arrays are staged on the stream.
+  void spinor_mix_space(GpuExecutor* dn, const T* const* potential);
+  void spin_density_space(GpuExecutor* dn, T* const* density, T weight);
+
   void synchronize();
   bool synchronous() const { return synchronous_; }
   // Execute on `stream` (nullptr = the legacy default stream); work is then
@@ -227,6 +254,8 @@ private:
   std::unique_ptr<DeviceBuffer> recKernel_;  // stages a host kernel
   mutable int fanFits_ = -1;  // z line region fits the LDS twice (-1: not yet asked)
   std::unique_ptr<DeviceBuffer> fanBuf_[4];
+  mutable int spinorFits_ = -1;  // x line region fits the LDS twice (-1: not yet asked)
+  std::unique_ptr<DeviceBuffer> spinorBuf_;  // stages four host potential / density arrays
   bool fockFused_ = false;
   std::unique_ptr<DeviceBuffer> fockA_, fockB_, fockAcc_;  // stage host a, b, acc
   std::size_t space_elements() const;  // elements of the local space domain

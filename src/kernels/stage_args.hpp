@@ -243,6 +243,37 @@ void launch_z_values_fan_in(const ZArgs& a, bool complexKernel, cx<T>* output, T
 // acc[i] += in[i] over sparse values (composed value fan, identity kernel).
 template <typename T>
 void launch_values_add(cx<T>* acc, const cx<T>* in, long long count, hipStream_t stream);
+// Spinor operators (multi_transform_apply_local_spinor / accumulate_spin_density):
+// x stages of C2C plans that keep the rows of both components (up, down) of a
+// tile in LDS, in two regions of the engine's whole line LDS each.
+// x_spinor_fits: both regions and the x -> column table fit a workgroup's LDS
+// (the launchers throw otherwise); the engines that already take more than
+// half of it (the 1024-long shapes; the 512-long ones take 70 KB and fit) do not.
+// `potential` and `density` are four real arrays [localZ][Y][X]:
+// {v_uu, v_dd, v_ud_re, v_ud_im} and {n_uu, n_dd, n_ud_re, n_ud_im}.
+// Apply: in place on the intermediates up[s], dn[s] of `spinors` spinors
+// (blockIdx.z = spinor): inverse x FFTs, the 2x2 mix, forward x FFTs.
+// plainPotential: default-policy loads (a batch shares the potential).
+// Density: density += weights[s] * {|u|^2, |d|^2, u conj(d)} of the inverse x
+// FFTs; every workgroup loops over the spinors for its tile, in order.
+constexpr int kMaxSpinors = kMaxBatch / 2;
+template <typename T>
+bool x_spinor_fits(int n);
+template <typename T>
+void launch_x_spinor_apply(const XArgs& a, int spinors, cx<T>* const* up, cx<T>* const* dn,
+                           const T* const* potential, bool plainPotential, const cx<T>* tw,
+                           hipStream_t stream);
+template <typename T>
+void launch_x_spinor_density(const XArgs& a, int spinors, const cx<T>* const* up, const cx<T>* const* dn,
+                             const T* weights, T* const* density, const cx<T>* tw, hipStream_t stream);
+// Composed spinor paths, one pass over two complex space domains of `count`
+// elements: the in-place 2x2 mix, and the four-array density update.
+template <typename T>
+void launch_space_spinor_mix(cx<T>* up, cx<T>* dn, const T* const* potential, long long count,
+                             hipStream_t stream);
+template <typename T>
+void launch_space_spin_density(const cx<T>* up, const cx<T>* dn, T* const* density, T weight, long long count,
+                               hipStream_t stream);
 // Composed path, one pass each: space[i] = conj(a[i]) * b[i] and acc[i] +=
 // weight * a[i] * space[i] (interleaved complex or, realSpace, real arrays).
 template <typename T>

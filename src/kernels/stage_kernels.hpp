@@ -2188,6 +2188,364 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// ------------------------------------------------------------ spinor operators
+// Two-component spinors (up, down): the 2x2 Hermitian local potential
+// {v_uu, v_dd, v_ud = v_ud_re + i v_ud_im, v_du = conj(v_ud)} and the spin
+// density matrix {n_uu, n_dd, n_ud = up conj(down)}. The x stages keep the
+// rows of both components of a tile in LDS at once: region 0 (up) at the start
+// of the workgroup's LDS, region 1 (down) `region1` elements behind it, which
+// is the engine's whole line LDS (both halves of a ping-pong plan, both
+// buffers of Bluestein) rounded up to 16 bytes; the x -> column table follows
+// region 1. A workgroup's LDS limit and the bytes of a launch:
+constexpr std::size_t kSpinorLdsLimit = 160 * 1024;
+inline std::size_t spinor_region_bytes(std::size_t engineBytes) { return (engineBytes + 15) / 16 * 16; }
+inline std::size_t spinor_lds_bytes(std::size_t engineBytes, int n) {
+  return 2 * spinor_region_bytes(engineBytes) + static_cast<std::size_t>(n) * sizeof(int) + 16;
+}
+// Compile-time engines that can never fit twice are not instantiated (their
+// plans run composed): the 1024-long shapes of both precisions.
+template <class Eng>
+struct SpinorFits {
+  static constexpr bool value = true;
+};
+template <typename T, int N, int S, bool LF, bool TwPre>
+struct SpinorFits<CtEng<T, N, S, LF, TwPre>> {
+  static constexpr bool value =
+      2 * ((CtEng<T, N, S, LF, TwPre>::F::lds_bytes() + 15) / 16 * 16) + std::size_t(N) * sizeof(int) + 16 <=
+      kSpinorLdsLimit;
+};
+
+// Kernel arguments, by value: the intermediates of the spinors' members and
+// the four real arrays [localZ][Y][X] (potential, read; density, updated).
+template <typename T>
+struct SpinorApplyArgs {
+  cx<T>* up[kMaxSpinors];
+  cx<T>* dn[kMaxSpinors];
+  const T* v[4];  // v_uu, v_dd, v_ud_re, v_ud_im
+};
+template <typename T>
+struct SpinorDensityArgs {
+  const cx<T>* up[kMaxSpinors];
+  const cx<T>* dn[kMaxSpinors];
+  T w[kMaxSpinors];
+  T* n[4];  // n_uu, n_dd, n_ud_re, n_ud_im
+  int count;
+};
+
+// (u, d) -> (v_uu u + v_ud d, conj(v_ud) u + v_dd d), fixed operation order
+template <typename T>
+__device__ __forceinline__ void spinor_mix(cx<T>& u, cx<T>& d, T vuu, T vdd, T vre, T vim) {
+  const cx<T> ou = mk<T>(fma(vuu, u.x, fma(vre, d.x, -(vim * d.y))), fma(vuu, u.y, fma(vre, d.y, vim * d.x)));
+  const cx<T> od = mk<T>(fma(vdd, d.x, fma(vre, u.x, vim * u.y)), fma(vdd, d.y, fma(vre, u.y, -(vim * u.x))));
+  u = ou;
+  d = od;
+}
+
+// The 2x2 mix of both regions for idx in [0, total): lanes walk the rows
+// contiguously as in scale_rows, so the loads of the four potential arrays
+// coalesce; kApplyUnroll loads per array are in flight per lane. No LDS race:
+// lane idx reads src(idx) of region 0 and of region 1 and writes dst(idx) of
+// both, and no other lane touches those four slots: src = the inverse engine's
+// out_at and dst = the forward engine's in_at are, inside a region, either the
+// same slot (compile-time engines, in-place run-time plans, Bluestein) or
+// slots of the region's two disjoint halves (ping-pong run-time plans with an
+// odd pass count: every read in the second half, every write in the first),
+// and region 1 begins behind the whole of region 0, second half included.
+// Stream: the potential is read once (non-temporal); plain loads when the
+// spinors of a batch share it.
+template <bool Stream, typename T, class Src, class Dst>
+__device__ __forceinline__ void spinor_mix_rows(cx<T>* ldsU, cx<T>* ldsD, const T* __restrict__ vuu,
+                                                const T* __restrict__ vdd, const T* __restrict__ vre,
+                                                const T* __restrict__ vim, int total, Src src, Dst dst) {
+  for (int base = threadIdx.x; base < total; base += blockDim.x * kApplyUnroll) {
+    T w[4][kApplyUnroll];
+#pragma unroll
+    for (int u = 0; u < kApplyUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        if constexpr (Stream) {
+          w[0][u] = ld_stream_real(vuu + idx);
+          w[1][u] = ld_stream_real(vdd + idx);
+          w[2][u] = ld_stream_real(vre + idx);
+          w[3][u] = ld_stream_real(vim + idx);
+        } else {
+          w[0][u] = vuu[idx];
+          w[1][u] = vdd[idx];
+          w[2][u] = vre[idx];
+          w[3][u] = vim[idx];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kApplyUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        const int si = src(idx), di = dst(idx);
+        cx<T> pu = ldsU[si], pd = ldsD[si];
+        spinor_mix(pu, pd, w[0][u], w[1][u], w[2][u], w[3][u]);
+        ldsU[di] = pu;
+        ldsD[di] = pd;
+      }
+    }
+  }
+}
+
+// Fused spinor local-operator x stage (C2C), in place on the two intermediates
+// of spinor blockIdx.z. A workgroup owns the tile of x_apply_kernel (plane z,
+// rows y0..y0+B, every column) of BOTH components. In-place invariant: the
+// first passes of both inverse FFTs have read every element of both tiles
+// before either forward FFT stores any (the mix and its barriers lie in
+// between), and no other workgroup touches either tile; so out == in per
+// member is safe, and so is any order of the members' tiles in memory. The
+// component loops are not unrolled: one inlined copy of each FFT, with the
+// per-element arguments and the twiddle table pinned anew per component (as
+// loop invariants their column offsets would stay live across the loop, see
+// x_density_kernel).
+template <class Eng, class Fwd, typename T, bool StreamV>
+__global__ void __launch_bounds__(Eng::kBlock)
+    x_spinor_apply_kernel(Eng eng, Fwd fwd, XArgs a, SpinorApplyArgs<T> sp, int region1,
+                          const cx<T>* __restrict__ tw) {
+  SPFFT_LDS_DECL(T);
+  const int B = eng.lines();
+  const int n = eng.n();
+  int tx, ty;
+  block_tile(tx, ty);
+  const int zl = a.zBegin + ty;
+  const int y0 = tx * B;
+  const int r1 = pin_uniform(region1);
+  int* xCol = reinterpret_cast<int*>(lds + 2 * r1);
+  build_xcol(a, xCol, n);
+  const int yl = min(B, a.Y - y0);
+  const int s = blockIdx.z;
+  const long long tileOff = static_cast<long long>(zl) * a.interZStride + y0;
+#pragma unroll 1
+  for (int c = 0; c < 2; ++c) {
+    // per-element arguments pinned in scalar registers (see x_backward_kernel)
+    const int rowStride = pin_uniform(static_cast<int>(a.interStride)), nFreq = pin_uniform(a.nFreq);
+    const int dense = pin_uniform(x_dense(a) ? 1 : 0);
+    const cx<T>* twC = reinterpret_cast<const cx<T>*>(pin_uniform64(reinterpret_cast<long long>(tw)));
+    const cx<T>* tile = (c ? sp.dn[s] : sp.up[s]) + tileOff;
+    auto load = [&](int b, int pos) -> cx<T> {
+      if (b >= yl) return czero<T>();
+      const int col = dense ? (pos < nFreq ? pos : -1) : xCol[pos];
+      return col < 0 ? czero<T>() : ld_inter(&tile[col * rowStride + b]);
+    };
+    eng.global_to_lds(lds + c * r1, twC, load);  // rows at out_at(b, x); ends with a barrier
+  }
+  const long long vOff = (static_cast<long long>(zl) * a.Y + y0) * n;
+  spinor_mix_rows<StreamV>(lds, lds + r1, sp.v[0] + vOff, sp.v[1] + vOff, sp.v[2] + vOff, sp.v[3] + vOff,
+                           yl * n, [&](int idx) {
+    const int b = idx / n;
+    return eng.out_at(b, idx - b * n);
+  }, [&](int idx) {
+    const int b = idx / n;
+    return fwd.in_at(b, idx - b * n);
+  });
+  __syncthreads();
+#pragma unroll 1
+  for (int c = 0; c < 2; ++c) {
+    const int rowStride = pin_uniform(static_cast<int>(a.interStride)), nFreq = pin_uniform(a.nFreq);
+    const int dense = pin_uniform(x_dense(a) ? 1 : 0);
+    const cx<T>* twC = reinterpret_cast<const cx<T>*>(pin_uniform64(reinterpret_cast<long long>(tw)));
+    cx<T>* tile = (c ? sp.dn[s] : sp.up[s]) + tileOff;
+    auto store = [&](int b, int pos, cx<T> v) {
+      const int col = dense ? (pos < nFreq ? pos : -1) : xCol[pos];
+      if (col >= 0 && b < yl) st_inter(&tile[col * rowStride + b], v);
+    };
+    fwd.lds_to_global(lds + c * r1, twC, store);
+  }
+}
+
+// n_uu += w |u|^2, n_dd += w |d|^2, n_ud += w u conj(d) for one element
+template <typename T>
+__device__ __forceinline__ void spin_density_add(T w, cx<T> u, cx<T> d, T& nuu, T& ndd, T& nre, T& nim) {
+  nuu = fma(w, norm2(u), nuu);
+  ndd = fma(w, norm2(d), ndd);
+  nre = fma(w, fma(u.x, d.x, u.y * d.y), nre);
+  nim = fma(w, fma(u.y, d.x, -(u.x * d.y)), nim);
+}
+
+// The four-array update for idx in [0, total), rows walked contiguously as in
+// density_rows. x_spinor_density_kernel carries four values per element where
+// x_density_kernel carries one, so the unroll is kDensityUnroll / 2: eight
+// loads in flight per lane before the first dependent store, twice those of
+// density_rows, at twice its registers (an unroll of 4 would hold sixteen
+// values, the doubling that spilled x_density_kernel at N = 1024).
+constexpr int kSpinDensityUnroll = 2;
+template <bool Stream, typename T, class Src>
+__device__ __forceinline__ void spin_density_rows(const cx<T>* ldsU, const cx<T>* ldsD, T* __restrict__ nuu,
+                                                  T* __restrict__ ndd, T* __restrict__ nre,
+                                                  T* __restrict__ nim, T w, int total, Src src) {
+  for (int base = threadIdx.x; base < total; base += blockDim.x * kSpinDensityUnroll) {
+    T r[4][kSpinDensityUnroll];
+#pragma unroll
+    for (int u = 0; u < kSpinDensityUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        if constexpr (Stream) {
+          r[0][u] = ld_stream_real(nuu + idx);
+          r[1][u] = ld_stream_real(ndd + idx);
+          r[2][u] = ld_stream_real(nre + idx);
+          r[3][u] = ld_stream_real(nim + idx);
+        } else {
+          r[0][u] = nuu[idx];
+          r[1][u] = ndd[idx];
+          r[2][u] = nre[idx];
+          r[3][u] = nim[idx];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kSpinDensityUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        const int si = src(idx);
+        spin_density_add(w, ldsU[si], ldsD[si], r[0][u], r[1][u], r[2][u], r[3][u]);
+        if constexpr (Stream) {
+          st_stream_real(nuu + idx, r[0][u]);
+          st_stream_real(ndd + idx, r[1][u]);
+          st_stream_real(nre + idx, r[2][u]);
+          st_stream_real(nim + idx, r[3][u]);
+        } else {
+          nuu[idx] = r[0][u];
+          ndd[idx] = r[1][u];
+          nre[idx] = r[2][u];
+          nim[idx] = r[3][u];
+        }
+      }
+    }
+  }
+}
+
+// Registers a lane may spend on the accumulators of the register path below
+// (32-bit registers: four values per element, two registers per fp64 value):
+// an eighth of the lane's register file at the kernel's launch bound, 64 for
+// workgroups of up to 256 threads (8 elements per lane in fp64, 16 in fp32),
+// 32 for the wider shapes, whose waves share a SIMD's registers two by two.
+// With 64 everywhere the fp32 N = 512 and N = 360 shapes (512 and 384
+// threads, 15-16 elements per lane) spilled 84 B per lane.
+template <class Eng>
+constexpr int spin_density_acc_regs() {
+  return Eng::kBlock <= kMaxThreads ? 64 : 32;
+}
+
+// Fused spin-density x stage (C2C). Tile ownership of x_density_kernel: the
+// workgroup owns plane z, rows y0..y0+B of the four density arrays, so no
+// atomics; it loops over the sp.count spinors of the launch with both
+// components' rows in LDS (regions 0 and 1), and lane idx updates the same
+// elements for every spinor, in spinor order: the sum order is fixed. Full
+// tiles of compile-time engines whose accumulators fit spin_density_acc_regs sum
+// in registers and touch the arrays once; otherwise every spinor's update goes
+// to the arrays, ordered by the lane's own program order. Stream: the cache
+// policy of the array accesses of a single-spinor launch.
+template <class Eng, typename T, bool Stream>
+__global__ void __launch_bounds__(Eng::kBlock)
+    x_spinor_density_kernel(Eng eng, XArgs a, SpinorDensityArgs<T> sp, int region1,
+                            const cx<T>* __restrict__ tw) {
+  SPFFT_LDS_DECL(T);
+  const int B = eng.lines();
+  const int n = eng.n();
+  int tx, ty;
+  block_tile(tx, ty);
+  const int zl = a.zBegin + ty;
+  const int y0 = tx * B;
+  const int r1 = pin_uniform(region1);
+  int* xCol = reinterpret_cast<int*>(lds + 2 * r1);
+  build_xcol(a, xCol, n);
+  const int yl = min(B, a.Y - y0);
+  const long long tileOff = static_cast<long long>(zl) * a.interZStride + y0;
+  const long long nOff = (static_cast<long long>(zl) * a.Y + y0) * n;
+  T* nuu = sp.n[0] + nOff;
+  T* ndd = sp.n[1] + nOff;
+  T* nre = sp.n[2] + nOff;
+  T* nim = sp.n[3] + nOff;
+  // inverse x FFTs of spinor m's two tiles: rows at out_at(b, x) of regions 0 and 1
+  auto spinor_fft = [&](int m) {
+    if (m > 0) __syncthreads();  // the previous spinor's rows have been read
+#pragma unroll 1
+    for (int c = 0; c < 2; ++c) {
+      // pinned anew per component and spinor (see x_density_kernel's band loop)
+      const int rowStride = pin_uniform(static_cast<int>(a.interStride)), nFreq = pin_uniform(a.nFreq);
+      const int dense = pin_uniform(x_dense(a) ? 1 : 0);
+      const cx<T>* twC = reinterpret_cast<const cx<T>*>(pin_uniform64(reinterpret_cast<long long>(tw)));
+      const cx<T>* tile = (c ? sp.dn[m] : sp.up[m]) + tileOff;
+      auto load = [&](int b, int pos) -> cx<T> {
+        if (b >= yl) return czero<T>();
+        const int col = dense ? (pos < nFreq ? pos : -1) : xCol[pos];
+        return col < 0 ? czero<T>() : ld_inter(&tile[col * rowStride + b]);
+      };
+      eng.global_to_lds(lds + c * r1, twC, load);  // ends with a barrier
+    }
+  };
+  auto row_at = [&](int idx) {
+    const int b = idx / n;
+    return eng.out_at(b, idx - b * n);
+  };
+  const int count = pin_uniform(sp.count);
+  if constexpr (!Eng::kBatchedCopy && !Stream) {
+    using F = typename Eng::F;
+    constexpr bool kEven = (F::B * Eng::kN) % F::NT == 0;
+    constexpr int kIters = kEven ? F::B * Eng::kN / F::NT : 1;
+    constexpr bool kRegs = kEven && 4 * kIters * static_cast<int>(sizeof(T) / 4) <= spin_density_acc_regs<Eng>();
+    if (kRegs && yl == F::B) {
+      T acc[4][kIters];
+#pragma unroll
+      for (int i = 0; i < kIters; ++i) acc[0][i] = acc[1][i] = acc[2][i] = acc[3][i] = T(0);
+      for (int m = 0; m < count; ++m) {
+        spinor_fft(m);
+        const T w = sp.w[m];
+#pragma unroll
+        for (int i = 0; i < kIters; ++i) {
+          const int si = row_at(static_cast<int>(threadIdx.x) + i * F::NT);
+          spin_density_add(w, lds[si], lds[r1 + si], acc[0][i], acc[1][i], acc[2][i], acc[3][i]);
+        }
+      }
+      T* arr[4] = {nuu, ndd, nre, nim};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int i = 0; i < kIters; ++i) acc[k][i] += arr[k][static_cast<int>(threadIdx.x) + i * F::NT];
+#pragma unroll
+        for (int i = 0; i < kIters; ++i) arr[k][static_cast<int>(threadIdx.x) + i * F::NT] = acc[k][i];
+      }
+      return;
+    }
+  }
+  for (int m = 0; m < count; ++m) {
+    spinor_fft(m);
+    spin_density_rows<Stream>(lds, lds + r1, nuu, ndd, nre, nim, sp.w[m], yl * n, row_at);
+  }
+}
+
+// Composed spinor paths, one pass over two complex space domains: the in-place
+// 2x2 mix, and the four-array density update.
+template <typename T>
+__global__ void __launch_bounds__(256)
+    space_spinor_mix_kernel(cx<T>* up, cx<T>* dn, const T* vuu, const T* vdd, const T* vre, const T* vim,
+                            long long count) {
+  const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
+  for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride) {
+    cx<T> u = ld_stream(up + i), d = ld_stream(dn + i);
+    spinor_mix(u, d, vuu[i], vdd[i], vre[i], vim[i]);
+    st_stream(up + i, u);
+    st_stream(dn + i, d);
+  }
+}
+template <typename T>
+__global__ void __launch_bounds__(256)
+    space_spin_density_kernel(const cx<T>* __restrict__ up, const cx<T>* __restrict__ dn, T* nuu, T* ndd,
+                              T* nre, T* nim, T w, long long count) {
+  const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
+  for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride) {
+    T a = nuu[i], b = ndd[i], c = nre[i], e = nim[i];
+    spin_density_add(w, ld_stream(up + i), ld_stream(dn + i), a, b, c, e);
+    nuu[i] = a;
+    ndd[i] = b;
+    nre[i] = c;
+    nim[i] = e;
+  }
+}
+
 // ------------------------------------------------ exchange (Fock) pair operator
 // accumulate_fock: acc += w a backward(K forward(conj(a) b)). Fused plans (C2C)
 // form the pair density in the forward x stage's row loads and accumulate in

@@ -523,6 +523,107 @@ void launch_z_values_fan_in(const ZArgs& a, bool complexKernel, cx<T>* output, T
   });
 }
 
+// Spinor x stages: the grid of launch_x_apply / launch_x_density, the LDS of
+// two line regions and the x -> column table (spinor_lds_bytes). The fit test
+// follows z_reciprocal_fan_fits: the engine's LDS without instantiating it.
+template <typename T>
+bool x_spinor_fits(int n) {
+  std::size_t fft = 0;
+  int lines = 0;
+  if (has_ct_kernel(n)) {
+    with_engine<T, +1, true>(n, [&](auto, int, int, std::size_t lds) { fft = lds; });
+  } else {
+    fft = in_lds_engine_bytes(n, sizeof(cx<T>), lines);
+  }
+  return spinor_lds_bytes(fft, n) <= kSpinorLdsLimit;
+}
+
+template <typename T>
+void launch_x_spinor_apply(const XArgs& a, int spinors, cx<T>* const* up, cx<T>* const* dn,
+                           const T* const* potential, bool plainPotential, const cx<T>* tw,
+                           hipStream_t stream) {
+  if (a.L <= a.zBegin || a.Y <= 0 || spinors < 1) return;
+  if (spinors > kMaxSpinors) throw InternalError();
+  SpinorApplyArgs<T> sp{};
+  for (int s = 0; s < spinors; ++s) {
+    sp.up[s] = up[s];
+    sp.dn[s] = dn[s];
+  }
+  for (int k = 0; k < 4; ++k) sp.v[k] = potential[k];
+  XArgs one = a;
+  one.batch.count = 0;
+  with_engine<T, +1, true>(a.n, [&](auto eng, int threads, int lines, std::size_t lds) {
+    using E = decltype(eng);
+    if constexpr (SpinorFits<E>::value) {
+      auto fwd = forward_twin(eng);
+      using F = decltype(fwd);
+      const std::size_t ldsTotal = spinor_lds_bytes(lds, a.n);
+      if (ldsTotal > kSpinorLdsLimit) throw InternalError();
+      auto k = plainPotential ? x_spinor_apply_kernel<E, F, T, false> : x_spinor_apply_kernel<E, F, T, true>;
+      prepare_kernel(k, ldsTotal);
+      hipLaunchKernelGGL(k, dim3(ceil_div(a.Y, lines), a.L - a.zBegin, static_cast<unsigned>(spinors)),
+                         dim3(threads), ldsTotal, stream, eng, fwd, one, sp,
+                         static_cast<int>(spinor_region_bytes(lds) / sizeof(cx<T>)), tw);
+      gpu_check_launch("x_spinor_apply", stream);
+    } else {
+      throw InternalError();
+    }
+  });
+}
+
+template <typename T>
+void launch_x_spinor_density(const XArgs& a, int spinors, const cx<T>* const* up, const cx<T>* const* dn,
+                             const T* weights, T* const* density, const cx<T>* tw, hipStream_t stream) {
+  if (a.L <= a.zBegin || a.Y <= 0 || spinors < 1) return;
+  if (spinors > kMaxSpinors) throw InternalError();
+  SpinorDensityArgs<T> sp{};
+  for (int s = 0; s < spinors; ++s) {
+    sp.up[s] = up[s];
+    sp.dn[s] = dn[s];
+    sp.w[s] = weights[s];
+  }
+  for (int k = 0; k < 4; ++k) sp.n[k] = density[k];
+  sp.count = spinors;
+  XArgs one = a;
+  one.batch.count = 0;
+  with_engine<T, +1, true>(a.n, [&](auto eng, int threads, int lines, std::size_t lds) {
+    using E = decltype(eng);
+    if constexpr (SpinorFits<E>::value) {
+      const std::size_t ldsTotal = spinor_lds_bytes(lds, a.n);
+      if (ldsTotal > kSpinorLdsLimit) throw InternalError();
+      // one spinor reads and writes the arrays once: streaming; the spinors of
+      // a batch revisit the tile: default-policy accesses
+      auto k = spinors > 1 ? x_spinor_density_kernel<E, T, false> : x_spinor_density_kernel<E, T, true>;
+      prepare_kernel(k, ldsTotal);
+      hipLaunchKernelGGL(k, dim3(ceil_div(a.Y, lines), a.L - a.zBegin, 1), dim3(threads), ldsTotal, stream, eng,
+                         one, sp, static_cast<int>(spinor_region_bytes(lds) / sizeof(cx<T>)), tw);
+      gpu_check_launch("x_spinor_density", stream);
+    } else {
+      throw InternalError();
+    }
+  });
+}
+
+template <typename T>
+void launch_space_spinor_mix(cx<T>* up, cx<T>* dn, const T* const* potential, long long count,
+                             hipStream_t stream) {
+  if (count <= 0) return;
+  const unsigned blocks = static_cast<unsigned>(std::min<long long>((count + 255) / 256, 256 * 64));
+  hipLaunchKernelGGL((space_spinor_mix_kernel<T>), dim3(blocks), dim3(256), 0, stream, up, dn, potential[0],
+                     potential[1], potential[2], potential[3], count);
+  gpu_check_launch("space_spinor_mix", stream);
+}
+
+template <typename T>
+void launch_space_spin_density(const cx<T>* up, const cx<T>* dn, T* const* density, T weight, long long count,
+                               hipStream_t stream) {
+  if (count <= 0) return;
+  const unsigned blocks = static_cast<unsigned>(std::min<long long>((count + 255) / 256, 256 * 64));
+  hipLaunchKernelGGL((space_spin_density_kernel<T>), dim3(blocks), dim3(256), 0, stream, up, dn, density[0],
+                     density[1], density[2], density[3], weight, count);
+  gpu_check_launch("space_spin_density", stream);
+}
+
 // acc[i] += in[i] over `count` sparse values (composed value fan, identity L)
 template <typename T>
 void launch_values_add(cx<T>* acc, const cx<T>* in, long long count, hipStream_t stream) {

@@ -24,7 +24,13 @@ composition of forward, multiply and backward, with --r2c on R2C transforms;
 --op tau / mgga times the kinetic-energy density and the local meta-GGA operator
 of one band on the wavefunction sphere, one multi_transform_accumulate_density_fan
 / multi_transform_apply_local_fan call against the best composition of torch
-multiplies and multi_transform_accumulate_density / multi_transform_apply_local.)
+multiplies and multi_transform_accumulate_density / multi_transform_apply_local;
+--op spinor / spin_density times the 2x2 local potential on two-component spinors
+and their spin density matrix, --transforms spinors (1 to 4) per
+multi_transform_apply_local_spinor / multi_transform_accumulate_spin_density call
+against multi_transform_backward, torch passes over the space domains and
+multi_transform_forward, and for the operator also against six apply_local
+members per spinor.)
 """
 import argparse
 import json
@@ -44,7 +50,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--unfused", action="store_true")
     ap.add_argument("--op", choices=("local", "density", "hartree", "fock", "gradient", "divergence",
-                                     "tau", "mgga"), default="local")
+                                     "tau", "mgga", "spinor", "spin_density"), default="local")
     ap.add_argument("--grid", type=int, default=0,
                     help="FFT grid N^3 instead of the density grid of the cutoff (the cutoff "
                          "sphere may then reach N/2, the transforms' own minimum grid)")
@@ -58,8 +64,12 @@ def main():
     basis = PlaneWaveBasis(alat=a.alat, ecut=a.ecut,
                            fft_dims=(a.grid,) * 3 if a.grid else None)
     model = PlaneWaveModel(basis, processing_unit=sp.ProcessingUnit.GPU,
-                           num_transforms=1 if a.op in ("fock", "gradient", "divergence", "tau", "mgga")
+                           num_transforms=1 if a.op in ("fock", "gradient", "divergence", "tau", "mgga",
+                                                        "spinor", "spin_density")
                            else a.transforms)
+    if a.op in ("spinor", "spin_density"):
+        spinor(a, basis, model)
+        return
     if a.op in ("tau", "mgga"):
         values_fan(a, basis, model)
         return
@@ -589,6 +599,122 @@ def values_fan(a, basis, model):
                       "ratio_composed_over_fused": med["composed"] / med["fused"],
                       "host_scope_median_s": scopes,
                       "model_bytes": model_bytes,
+                      "model_ratio_composed": model_bytes["composed"] / model_bytes["fused"]}),
+          flush=True)
+
+
+def spinor(a, basis, model):
+    """--op spinor / spin_density: S = --transforms two-component spinors per call on the
+    wavefunction sphere, in alternating rounds of one process (medians over at least 7
+    rounds):
+      fused     one multi_transform_apply_local_spinor / multi_transform_accumulate_spin_density
+                call on 2 S transforms;
+      composed  multi_transform_backward of the 2 S members, torch passes over the space
+                domains (operator: per component one multiply and one addcmul with the
+                complex off-diagonal field formed beforehand, and a copy back; density:
+                four in-place updates), and for the operator multi_transform_forward;
+      six       (operator) one multi_transform_apply_local call of 6 S members, v_uu, v_ud_re
+                and v_ud_im on the one component and v_ud_re, v_ud_im and v_dd on the other,
+                combined by torch passes over the values.
+    Prints microseconds per call, the ratio against the faster composition, the host scopes
+    of the fused call and the modelled x stage bytes per grid point (fp64: operator fused
+    2*16 read + 2*16 write of the intermediates + 4*8 potential = 96 B, composed 2*32
+    x_backward + 2*32 x_forward + at least 2*16 + 4*8 + 2*16 for the mix = 224 B; density
+    fused 2*16 + 4*2*8 = 96 B, composed 2*32 + at least 2*16 + 4*2*8 = 160 B)."""
+    import torch
+
+    import spfft_amd as sp
+    nx, ny, nz = basis.fft_dims
+    S = max(1, min(4, a.transforms))
+    op = a.op == "spinor"
+    ts = model._wave_transforms(2 * S)
+    ts6 = model._wave_transforms(6 * S) if op else None
+    g = torch.Generator(device="cuda")
+    g.manual_seed(11)
+    cs = [torch.randn(basis.num_pw, dtype=torch.complex128, device="cuda", generator=g) for _ in range(2 * S)]
+    v4 = torch.rand((4, nz, ny, nx), dtype=torch.float64, device="cuda", generator=g)
+    vud = torch.complex(v4[2], v4[3])
+    vdu = vud.conj().resolve_conj()
+    m4 = torch.zeros((4, nz, ny, nx), dtype=torch.float64, device="cuda")
+    outs = [torch.empty_like(c) for c in cs]
+    ws = [1.0 + 0.25 * s for s in range(S)]
+    full = sp.Scaling.FULL
+    pots6 = [v4[0], v4[2], v4[3], v4[2], v4[3], v4[1]] * S
+
+    def call(variant):
+        if variant == "fused":
+            if op:
+                return sp.multi_transform_apply_local_spinor(ts, cs, v4, outputs=outs, scaling=full)
+            return sp.multi_transform_accumulate_spin_density(ts, cs, ws, m4)
+        if variant == "six":
+            ins = []
+            for s in range(S):
+                u, d = cs[2 * s], cs[2 * s + 1]
+                ins += [u, d, d, u, u, d]
+            r = sp.multi_transform_apply_local(ts6, ins, pots6, scalings=[full] * (6 * S))
+            res = []
+            for s in range(S):
+                q = r[6 * s:6 * s + 6]
+                res.append(torch.add(q[0] + q[1], q[2], alpha=1j))
+                res.append(torch.add(q[3] + q[5], q[4], alpha=-1j))
+            return res
+        spaces = sp.multi_transform_backward(ts, cs)
+        if op:
+            for u, d in zip(spaces[0::2], spaces[1::2]):
+                nu = torch.addcmul(u * v4[0], d, vud)
+                nd = torch.addcmul(d * v4[1], u, vdu)
+                u.copy_(nu)
+                d.copy_(nd)
+            return sp.multi_transform_forward(ts, outputs=outs, scalings=[full] * (2 * S))
+        for u, d, w in zip(spaces[0::2], spaces[1::2], ws):
+            ur, dr = torch.view_as_real(u), torch.view_as_real(d)
+            m4[0].add_((ur * ur).sum(-1), alpha=w)
+            m4[1].add_((dr * dr).sum(-1), alpha=w)
+            ud = torch.view_as_real(u * d.conj())
+            m4[2].add_(ud[..., 0], alpha=w)
+            m4[3].add_(ud[..., 1], alpha=w)
+        return m4
+    variants = ("fused", "composed", "six") if op else ("fused", "composed")
+    rounds, calls = max(7, a.reps), 10
+    times = {v: [] for v in variants}
+    for v in variants:
+        call(v)
+    for r in range(rounds):
+        for v in (variants if r % 2 == 0 else variants[::-1]):  # mirrored orders
+            torch.cuda.synchronize()
+            t0_ = time.perf_counter()
+            for _ in range(calls):
+                call(v)
+            torch.cuda.synchronize()
+            times[v].append((time.perf_counter() - t0_) / calls)
+    med = {v: sorted(x)[len(x) // 2] for v, x in times.items()}
+    sp.timing_reset()
+    sp.timing_enable(True)
+    try:
+        for _ in range(calls):
+            call("fused")
+        torch.cuda.synchronize()
+        tree = sp.timing_json()
+        scopes = _scope_medians(tree, {
+            "multi_apply_local_spinor", "multi_accumulate_spin_density", "gpu_apply_local_spinor_batch",
+            "gpu_accumulate_spin_density_batch"})
+        stages = _gpu_stage_medians(tree)
+    finally:
+        sp.timing_enable(False)
+    best = min(med[v] for v in variants if v != "fused")
+    model_bytes = {"fused": 96, "composed": 224} if op else {"fused": 96, "composed": 160}
+    print(json.dumps({"workload": "plane-wave " + a.op, "fft_dims": list(basis.fft_dims),
+                      "num_values": basis.num_pw, "spinors": S,
+                      "batch": os.environ.get("SPFFT_BATCH", "1"),
+                      "spinor_fused": ts[0].spinor_fused,
+                      "rounds": rounds, "calls_per_round": calls,
+                      "median_us": {v: 1e6 * x for v, x in med.items()},
+                      "min_us": {v: 1e6 * min(x) for v, x in times.items()},
+                      "max_us": {v: 1e6 * max(x) for v, x in times.items()},
+                      "ratio_best_composition_over_fused": best / med["fused"],
+                      "host_scope_median_s": scopes,
+                      "gpu_stage_median_s": stages,
+                      "model_x_stage_bytes_per_point": model_bytes,
                       "model_ratio_composed": model_bytes["composed"] / model_bytes["fused"]}),
           flush=True)
 
