@@ -142,9 +142,15 @@ SPFFT_EXPORT SpfftError spfft_amd_float_transform_backward_xy(SpfftFloatTransfor
  * float as the transform). input, potential and output are host or device
  * pointers (device pointers are used in place, as backward does for its input);
  * input == output is allowed. After the call the contents of the space domain
- * are unspecified: fused plans (C2C transforms whose x lines fit one workgroup)
- * never form it and leave it untouched, other plans (R2C, long x lines) pass
- * through it. A null potential is SPFFT_INVALID_PARAMETER_ERROR, except on a
+ * are unspecified: fused plans never form it and leave it untouched, other
+ * plans pass through it. Fused are C2C transforms whose x lines fit one
+ * workgroup, and R2C transforms with even dimX whose half-length dimX / 2 has a
+ * compile-time kernel (the powers of two 16..1024 and the mixed-radix lengths
+ * of the build; SPFFT_R2C_FUSE=0 or SPFFT_R2C_PACKED=0 at creation keeps them
+ * composed). Odd dimX, other half-lengths, long x lines and host transforms run
+ * composed. On a fused R2C plan the potential is read as pairs of elements: a
+ * call whose potential is not aligned to 2 * sizeof(element) runs composed. A
+ * null potential is SPFFT_INVALID_PARAMETER_ERROR, except on a
  * rank without local planes, whose space domain is empty. */
 SPFFT_EXPORT SpfftError spfft_amd_transform_apply_local(SpfftTransform t, const double* input,
                                                         const double* potential, double* output,
@@ -153,7 +159,8 @@ SPFFT_EXPORT SpfftError spfft_amd_float_transform_apply_local(SpfftFloatTransfor
                                                               const float* input,
                                                               const float* potential, float* output,
                                                               SpfftScalingType scaling);
-/* *fused = 1 if the plan runs the fused x apply stage on the GPU, else 0. */
+/* *fused = 1 if the plan runs the fused x apply stage on the GPU (C2C, or the
+ * packed-real stage of the R2C plans named above), else 0. */
 SPFFT_EXPORT SpfftError spfft_amd_transform_apply_local_fused(SpfftTransform t, int* fused);
 SPFFT_EXPORT SpfftError spfft_amd_float_transform_apply_local_fused(SpfftFloatTransform t,
                                                                     int* fused);
@@ -174,8 +181,11 @@ SPFFT_EXPORT SpfftError spfft_amd_float_multi_transform_apply_local(
  * value is real and the contribution weight * s^2). density is a host or device
  * pointer, is updated in place and is never zeroed by the library; input is not
  * modified. After the call the contents of the space domain are unspecified:
- * fused plans (C2C transforms whose x lines fit one workgroup) never form it
- * and leave it untouched, other plans (R2C, long x lines) pass through it. A
+ * fused plans never form it and leave it untouched, other plans pass through
+ * it; which plans are fused is as for spfft_amd_transform_apply_local (C2C with
+ * x lines of one workgroup; R2C with even dimX and a compile-time half-length
+ * kernel). On a fused R2C plan density is updated as pairs of elements: a call
+ * whose density is not aligned to 2 * sizeof(element) runs composed. A
  * null density with local planes is SPFFT_INVALID_PARAMETER_ERROR. */
 SPFFT_EXPORT SpfftError spfft_amd_transform_accumulate_density(SpfftTransform t,
                                                                const double* input, double weight,
@@ -183,7 +193,8 @@ SPFFT_EXPORT SpfftError spfft_amd_transform_accumulate_density(SpfftTransform t,
 SPFFT_EXPORT SpfftError spfft_amd_float_transform_accumulate_density(SpfftFloatTransform t,
                                                                      const float* input,
                                                                      float weight, float* density);
-/* *fused = 1 if the plan runs the fused x density stage on the GPU, else 0. */
+/* *fused = 1 if the plan runs the fused x density stage on the GPU (C2C, or the
+ * packed-real stage of the R2C plans named above), else 0. */
 SPFFT_EXPORT SpfftError spfft_amd_transform_density_fused(SpfftTransform t, int* fused);
 SPFFT_EXPORT SpfftError spfft_amd_float_transform_density_fused(SpfftFloatTransform t, int* fused);
 /* density += sum_i weights[i] * |backward_i(inputs[i])|^2 of n transforms

@@ -461,7 +461,8 @@ class _TransformBase:
 
     @property
     def apply_local_fused(self) -> bool:
-        """True if apply_local runs the fused x stage (GPU, C2C, x lines of one workgroup)."""
+        """True if apply_local runs the fused x stage (GPU; C2C with x lines of one workgroup,
+        or R2C with even dim_x whose half-length has a compile-time kernel)."""
         c = self._cache.get("apply_local_fused")
         if c is None:
             v = ctypes.c_int()
@@ -486,8 +487,8 @@ class _TransformBase:
 
     @property
     def density_fused(self) -> bool:
-        """True if accumulate_density runs the fused x stage (GPU, C2C, x lines of one
-        workgroup)."""
+        """True if accumulate_density runs the fused x stage (GPU; C2C with x lines of one
+        workgroup, or R2C with even dim_x whose half-length has a compile-time kernel)."""
         c = self._cache.get("density_fused")
         if c is None:
             v = ctypes.c_int()

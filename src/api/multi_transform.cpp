@@ -166,6 +166,7 @@ void multi_apply_local(const std::vector<TransformImpl<T>*>& ts, const T* const*
       ts,
       [&](int i) {
         return ts[i]->apply_local_fused() && is_device_pointer(potentials[i]) &&
+               ts[i]->gpu()->pairs_aligned(potentials[i]) &&
                (ts[i]->plan().numLocalElements == 0 ||
                 (is_device_pointer(inputs[i]) && is_device_pointer(outputs[i])));
       },
@@ -231,7 +232,7 @@ void multi_accumulate_density(const std::vector<TransformImpl<T>*>& ts, const T*
   const std::vector<bool> batched = run_batches<T>(
       ts,
       [&](int i) {
-        return ts[i]->density_fused() && deviceRho &&
+        return ts[i]->density_fused() && deviceRho && ts[i]->gpu()->pairs_aligned(density) &&
                (ts[i]->plan().numLocalElements == 0 || is_device_pointer(inputs[i]));
       },
       [](int) { return 0; },

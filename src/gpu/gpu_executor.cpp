@@ -66,13 +66,15 @@ GpuExecutor<T>::GpuExecutor(std::shared_ptr<GridImpl<T>> grid,
   }
   setup_long_axes();
   // apply_local runs the fused x apply stage for C2C transforms whose x lines
-  // fit one workgroup; R2C (packed-real pair) and long x lines run unfused
-  applyFused_ = p.type == SPFFT_TRANS_C2C && !longX_;
+  // fit one workgroup; long x lines run unfused, R2C plans are decided below
+  // (r2cFused_), once the packed-real stage is known
+  c2cFused_ = p.type == SPFFT_TRANS_C2C && !longX_;
+  applyFused_ = c2cFused_;
   // accumulate_density runs the fused x density stage under the same conditions
   densityFused_ = applyFused_;
-  // accumulate_fock runs the fused pair x stages under the same conditions (its
-  // z stage follows reciprocalFused_ independently)
-  fockFused_ = applyFused_;
+  // accumulate_fock runs the fused pair x stages of C2C plans only (its z stage
+  // follows reciprocalFused_ independently)
+  fockFused_ = c2cFused_;
   // apply_reciprocal runs the fused z stage for simple sticks whose z lines fit
   // one workgroup, on a stick side that is not a *_FLOAT exchange buffer and that
   // peers do not write (peerWrites_ is known only further down: see below)
@@ -120,6 +122,13 @@ GpuExecutor<T>::GpuExecutor(std::shared_ptr<GridImpl<T>> grid,
       env_int("SPFFT_R2C_PACKED", 1, 0, 1) && (dev::has_ct_kernel(p.dimX / 2) ||
                                                 p.dimX / 2 <= dev::max_device_fft_length(sizeof(T) == 8)))
     upload(twXh_, make_twiddles<T>(p.dimX / 2));
+  // R2C: apply_local and accumulate_density run the fused packed-real x stages
+  // when the packed-real stage is in use and its half-length has a compile-time
+  // engine with those kernels (SPFFT_R2C_FUSE=0 keeps the composed path). Odd
+  // dimX, run-time and Bluestein half-lengths and long x lines stay composed.
+  r2cFused_ = twXh_ && !longX_ && dev::has_ct_kernel(p.dimX / 2) && dev::x_r2c_fused_fits<T>(p.dimX) &&
+              env_int("SPFFT_R2C_FUSE", 1, 0, 1) != 0;
+  if (r2cFused_) applyFused_ = densityFused_ = true;
   upload(twY_, make_twiddles<T>(p.dimY));
   upload(twZ_, make_twiddles<T>(p.dimZ));
 
@@ -1402,13 +1411,32 @@ const T* GpuExecutor<T>::device_potential(const T* potential) {
   return potential_->data<T>();
 }
 
+// The x stage of the fused operators on this executor's stream: the C2C
+// kernels, or the packed-real ones of a fused R2C plan.
+template <typename T>
+void GpuExecutor<T>::x_apply_launch(const dev::XArgs& xa, const T* pot, cx<T>* tile, bool plainPotential) {
+  if (r2cFused_)
+    dev::launch_x_apply_r2c<T>(xa, pot, tile, plainPotential, twX_->data<cx<T>>(), twXh_->data<cx<T>>(), stream_);
+  else
+    dev::launch_x_apply<T>(xa, pot, tile, plainPotential, twX_->data<cx<T>>(), stream_);
+}
+
+template <typename T>
+void GpuExecutor<T>::x_density_launch(const dev::XArgs& xa, const cx<T>* tile, T* rho, const T* weights) {
+  if (r2cFused_)
+    dev::launch_x_density_r2c<T>(xa, tile, rho, weights, twX_->data<cx<T>>(), twXh_->data<cx<T>>(), stream_);
+  else
+    dev::launch_x_density<T>(xa, tile, rho, weights, twX_->data<cx<T>>(), stream_);
+}
+
 template <typename T>
 void GpuExecutor<T>::apply_local_xy(const T* potential) {
   SPFFT_TIMED_SCOPE("gpu_apply_local_xy");
   DeviceGuard guard(deviceId_);
   const IndexPlan& p = *plan_;
   const T* pot = device_potential(potential);
-  if (!applyFused_) {
+  // (a potential that cannot be read as pairs: this call of a fused R2C plan runs composed)
+  if (!applyFused_ || !pairs_aligned(pot)) {
     backward_xy(SPFFT_PU_GPU);
     dev::launch_space_scale<T>(grid_->device_slot(GridImpl<T>::kSpace), pot,
                                static_cast<long long>(p.local_planes()) * p.dimY * p.dimX,
@@ -1449,7 +1477,7 @@ void GpuExecutor<T>::apply_local_xy(const T* potential) {
         yb.plainSticks = plainHandoff_;
         cx<T>* tile = inter_for(inter, z0);
         y_backward_launch(yb, slab, tile);
-        dev::launch_x_apply<T>(xa, pot, tile, false, twX_->data<cx<T>>(), stream_);
+        x_apply_launch(xa, pot, tile, false);
         y_forward_launch(yf, tile, slab);
       }
       if (pipe) chunkEv_[k]->record(stream_);  // chunk k may leave
@@ -1492,7 +1520,8 @@ void GpuExecutor<T>::accumulate_density_xy(T* density, T weight, GpuExecutor* af
     gpu_check(hipMemcpyAsync(rho, density, count * sizeof(T), hipMemcpyHostToDevice, stream_),
               "hipMemcpyAsync");
   }
-  if (!densityFused_) {
+  // (a rho that cannot be accessed as pairs: this call of a fused R2C plan runs composed)
+  if (!densityFused_ || !pairs_aligned(rho)) {
     backward_xy(SPFFT_PU_GPU);
     order_after_density(after);
     dev::launch_space_density<T>(grid_->device_slot(GridImpl<T>::kSpace), rho, weight,
@@ -1504,7 +1533,7 @@ void GpuExecutor<T>::accumulate_density_xy(T* density, T weight, GpuExecutor* af
     backward_yx_ranges([&](const dev::XArgs& xa, cx<T>* tile) {
       order_after_density(after);  // (once: the stream stays behind it)
       after = nullptr;
-      dev::launch_x_density<T>(xa, tile, rho, &weight, twX_->data<cx<T>>(), stream_);
+      x_density_launch(xa, tile, rho, &weight);
     });
   }
   if (staged)
@@ -1794,8 +1823,7 @@ void GpuExecutor<T>::apply_local_batch_middle(dev::YArgs ya, const dev::BatchPtr
     // (the scope names the kernel variant: plain loads of a shared potential measured
     // +1% against streaming ones at 256^3, 8 bands per call; profiles/r7/apply_local)
     SPFFT_TIMED_SCOPE(shared ? "x_apply_shared_potential" : "x_apply_streamed_potential");
-    dev::launch_x_apply<T>(xa, static_cast<const T*>(xb.in[0]), static_cast<cx<T>*>(xb.out[0]), shared,
-                           twX_->data<cx<T>>(), s);
+    x_apply_launch(xa, static_cast<const T*>(xb.in[0]), static_cast<cx<T>*>(xb.out[0]), shared);
   }
   ya.batch = yf;
   dev::launch_y_forward<T, cx<T>>(ya, static_cast<const cx<T>*>(yf.in[0]),
@@ -1812,8 +1840,7 @@ void GpuExecutor<T>::density_batch_middle(dev::YArgs ya, const dev::BatchPtrs& y
   dev::launch_y_backward<T, cx<T>>(ya, static_cast<const cx<T>*>(yb.in[0]),
                                    static_cast<cx<T>*>(yb.out[0]), twY_->data<cx<T>>(), s);
   order_after_density(after);
-  dev::launch_x_density<T>(xa, static_cast<const cx<T>*>(xb.in[0]), density, weights.data(),
-                           twX_->data<cx<T>>(), s);
+  x_density_launch(xa, static_cast<const cx<T>*>(xb.in[0]), density, weights.data());
 }
 
 // One launch per stage for a batch of fused plans: z backward, y backward,
@@ -1848,6 +1875,7 @@ void GpuExecutor<T>::apply_local_batch(const std::vector<GpuExecutor*>& ex,
       throw InvalidParameterError();
     if (p.local_planes() > 0 && (!potentials[i] || !is_device_pointer(potentials[i])))
       throw InvalidParameterError();
+    if (!e->pairs_aligned(potentials[i])) throw InternalError();
     shared = shared && potentials[i] == potentials[0];
     void* stick = e->grid_->device_slot(GridImpl<T>::kStickSide);
     void* slab = e->grid_->device_slot(GridImpl<T>::kSlabSide);
@@ -1895,6 +1923,7 @@ void GpuExecutor<T>::accumulate_density_batch(const std::vector<GpuExecutor*>& e
     if (!e->batchable() || !e->densityFused_ || e->batchKey_ != l->batchKey_) throw InternalError();
   const IndexPlan& p = *l->plan_;
   if (p.local_planes() > 0 && (!density || !is_device_pointer(density))) throw InvalidParameterError();
+  if (!l->pairs_aligned(density)) throw InternalError();
   batch_join(ex);
   dev::BatchPtrs zb{}, yb{}, xb{};
   zb.count = yb.count = xb.count = n;
@@ -2161,7 +2190,7 @@ void GpuExecutor<T>::download_values(T* hostDst, const cx<T>* src) {
 // ------------------------------------------------------------------ value fans
 template <typename T>
 bool GpuExecutor<T>::values_fan_fused() const {
-  return reciprocal_fan_fused() && applyFused_ && densityFused_;
+  return reciprocal_fan_fused() && c2cFused_;
 }
 
 namespace {
@@ -2301,7 +2330,7 @@ void GpuExecutor<T>::copy_values(T* dst, const T* src) {
 // ------------------------------------------------------------ spinor operators
 template <typename T>
 bool GpuExecutor<T>::spinor_fused() const {
-  if (!batchable() || !applyFused_ || !densityFused_) return false;
+  if (!batchable() || !c2cFused_) return false;
   if (spinorFits_ < 0) spinorFits_ = dev::x_spinor_fits<T>(plan_->dimX) ? 1 : 0;
   return spinorFits_ == 1;
 }

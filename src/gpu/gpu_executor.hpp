@@ -69,6 +69,12 @@ public:
   // host or device pointer.
   void apply_local_xy(const T* potential);
   bool apply_local_fused() const { return applyFused_; }
+  // The fused packed-real x stages of an R2C plan read the potential and update
+  // rho as pairs of real elements: true unless this is such a plan and p is not
+  // aligned to 2 * sizeof(T). A call with a misaligned array runs composed.
+  bool pairs_aligned(const void* p) const {
+    return !r2cFused_ || reinterpret_cast<std::uintptr_t>(p) % (2 * sizeof(T)) == 0;
+  }
   // batchable() fused plans with equal keys: one launch per stage (device pointers)
   static void apply_local_batch(const std::vector<GpuExecutor*>& ex, const std::vector<const T*>& inputs,
                                 const std::vector<const T*>& potentials, const std::vector<T*>& outputs,
@@ -240,6 +246,10 @@ private:
   const T* device_potential(const T* potential);  // stages a host potential
   std::unique_ptr<DeviceBuffer> potential_;
   bool applyFused_ = false;
+  bool c2cFused_ = false;  // C2C x stages of one workgroup (fock, spinor, value fans)
+  bool r2cFused_ = false;  // apply_local / accumulate_density on the packed-real x stages
+  void x_apply_launch(const dev::XArgs& xa, const T* pot, cx<T>* tile, bool plainPotential);
+  void x_density_launch(const dev::XArgs& xa, const cx<T>* tile, T* rho, const T* weights);
   std::unique_ptr<DeviceBuffer> density_;  // stages a host rho
   bool densityFused_ = false;
   void order_after_density(GpuExecutor* prev);  // this stream waits for prev's work so far

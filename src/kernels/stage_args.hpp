@@ -177,6 +177,23 @@ template <typename T>
 void launch_space_density(const void* space, T* density, T weight, long long count, bool realSpace,
                           hipStream_t stream);
 
+// Fused packed-real x stages of R2C transforms with even n whose half-length
+// n / 2 has a compile-time engine (x_r2c_fused_fits; the launchers throw
+// otherwise): launch_x_apply and launch_x_density on the rows y[m] = s[2m] +
+// i s[2m+1] of the packed-real stage, in place on the intermediate, the real
+// space domain neither read nor written. `tw` / `twHalf` as launch_x_backward.
+// The potential and the density are read and written as pairs (s[2m], s[2m+1]):
+// their pointers must be aligned to 2 * sizeof(T). Batched launches as their
+// C2C counterparts.
+template <typename T>
+bool x_r2c_fused_fits(int n);
+template <typename T>
+void launch_x_apply_r2c(const XArgs& a, const T* potential, cx<T>* inter, bool plainPotential,
+                        const cx<T>* tw, const cx<T>* twHalf, hipStream_t stream);
+template <typename T>
+void launch_x_density_r2c(const XArgs& a, const cx<T>* inter, T* density, const T* weights, const cx<T>* tw,
+                          const cx<T>* twHalf, hipStream_t stream);
+
 // Exchange (Fock) pair operator, fused x stages of C2C transforms. Forward: the
 // x stage of forward_xy whose rows are conj(a) * b of two space-domain arrays
 // [z][y][x]. Backward: the x stage of backward_xy whose result u is not stored:

@@ -2957,6 +2957,290 @@ __global__ void __launch_bounds__(Eng::kBlock)
   }
 }
 
+// ------------------------------------------- fused operators on packed-real rows
+// apply_local and accumulate_density of R2C transforms whose half-length h =
+// dimX / 2 has a compile-time engine: the x stages below work on the rows y[m] =
+// s[2m] + i s[2m+1] of the packed-real stage in LDS, and the real space domain
+// is neither read nor written. Compile-time engines only (the run-time and
+// Bluestein half-lengths stay composed): the C2R pre-pass rides on the first
+// pass's loads, as in x_backward_c2r_kernel.
+//
+// Engines whose fused packed-real kernels are not built; their plans run
+// composed (x_r2c_fused_fits).
+template <class Eng>
+struct R2cFuseFits {
+  static constexpr bool value = !Eng::kBatchedCopy;
+};
+
+// Inverse half-length FFT of the tile's packed-real rows with the C2R pre-pass
+// folded into the first-pass loads (the body of x_backward_c2r_kernel's
+// compile-time path, kept apart from it so that kernel's code is untouched):
+// Z[k] from X[k] and X[h-k], imaginary parts of X[0] and X[h] dropped, columns
+// without sticks read as zero. Row b ends at eng.out_at(b, m); ends with a
+// barrier. Every global load of the tile `src` happens here.
+template <class Eng, typename T>
+__device__ __forceinline__ void c2r_rows_to_lds(Eng eng, cx<T>* lds, const XArgs& a, const int* xCol,
+                                                const cx<T>* src, int yl, const cx<T>* __restrict__ twh,
+                                                const cx<T>* __restrict__ twn) {
+  const int h = eng.n();
+  // arguments of the per-element loads pinned in scalar registers (see x_backward_kernel)
+  const int rowStride = pin_uniform(static_cast<int>(a.interStride)), nFreq = pin_uniform(a.nFreq);
+  const int dense = pin_uniform(x_dense(a) ? 1 : 0);
+  auto col = [&](int k, int b) -> cx<T> {
+    const int c = dense ? (k < nFreq ? k : -1) : xCol[k];
+    return (c < 0 || b >= yl) ? czero<T>() : src[c * rowStride + b];
+  };
+  // (the twiddle of position k from one table entry per kk: see x_backward_c2r_kernel)
+  constexpr int R0 = FirstRadix<typename Eng::F>::value, Q = R0 ? Eng::kN / R0 : 1;
+  eng.global_to_lds(lds, twh, [&](int b, int k, int off) -> cx<T> {
+    cx<T> xk = col(k, b);
+    cx<T> xm = col(h - k, b);
+    if (k == 0) {
+      xk.y = T(0);
+      xm.y = T(0);
+    }
+    const cx<T> xmc = conj(xm);
+    const int r = off / Q;
+    cx<T> w = twn[k - r * Q];
+    if constexpr (R0 == 16) {
+      if (r) w = cmul(w, mk<T>(T(fftc::C32[r & 15]), T(-fftc::S32[r & 15])));
+    } else if constexpr (R0 == 8) {
+      if (r) w = cmul(w, mk<T>(T(fftc::C16[r & 15]), T(-fftc::S16[r & 15])));
+    } else {
+      w = twn[k];
+    }
+    return (xk + xmc) + rot<+1>(twm<+1>(xk - xmc, w));
+  });
+}
+
+// lds[dst(idx)] = {lds[src(idx)].x * v[idx].x, lds[src(idx)].y * v[idx].y} for
+// idx in [0, total): scale_rows on packed-real rows, the potential row read as
+// pairs (V[2m], V[2m+1]). Same walk, same kApplyUnroll loads in flight, and the
+// same reason for no LDS race: lane idx reads src(idx) and writes dst(idx), and
+// the kernel passes the inverse engine's out_at and its forward twin's in_at,
+// which are the same slot (compile-time engines on one layout, the
+// static_assert of forward_twin). `v` must be aligned to one pair.
+template <bool Stream, typename T, class Src, class Dst>
+__device__ __forceinline__ void scale_row_pairs(cx<T>* lds, const cx<T>* __restrict__ v, int total, Src src,
+                                                Dst dst) {
+  for (int base = threadIdx.x; base < total; base += blockDim.x * kApplyUnroll) {
+    cx<T> w[kApplyUnroll];
+#pragma unroll
+    for (int u = 0; u < kApplyUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        if constexpr (Stream) w[u] = ld_stream(v + idx);
+        else w[u] = v[idx];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kApplyUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        const cx<T> y = lds[src(idx)];
+        lds[dst(idx)] = mk<T>(y.x * w[u].x, y.y * w[u].y);
+      }
+    }
+  }
+}
+
+// Fused local-operator x stage (R2C, packed-real), in place on the [z][column][y]
+// intermediate: a workgroup owns the tile of x_backward_c2r_kernel (plane z,
+// rows y0..y0+B, columns 0..h).
+//  (a) C2R pre-pass in the first-pass loads + inverse half-length FFT,
+//  (b) y.x *= V[2m], y.y *= V[2m+1] in LDS,
+//  (c) forward half-length FFT on forward_twin(eng), LDS to LDS,
+//  (d) the post pass of x_forward_r2c_kernel over the pairs (k, h-k), Nyquist
+//      column included, columns without sticks skipped.
+// Invariant that makes the in-place update safe: every global load of the tile
+// happens in (a), every store in (d), the barriers of (a), (b) and (c) lie
+// between them, and no other workgroup touches the tile. (b) has no LDS race:
+// see scale_row_pairs. LDS: FFT lines | one unused element per line (the
+// Nyquist slot of the C2R launch, whose LDS and grid this launch takes) | xCol.
+template <class Eng, class Fwd, typename T, bool StreamV>
+__global__ void __launch_bounds__(Eng::kBlock)
+    x_apply_r2c_kernel(Eng eng, Fwd fwd, XArgs a, const T* __restrict__ potential, cx<T>* inter,
+                       const cx<T>* __restrict__ twh, const cx<T>* __restrict__ twn) {
+  static_assert(!Eng::kBatchedCopy, "x apply r2c: compile-time engines only");
+  SPFFT_LDS_DECL(T);
+  SPFFT_BATCH_SELECT(a, potential, inter);
+  const int B = eng.lines();
+  const int h = eng.n();
+  int tx, ty;
+  block_tile(tx, ty);
+  const int zl = a.zBegin + ty;
+  const int y0 = tx * B;
+  int* xCol = reinterpret_cast<int*>(reinterpret_cast<cx<T>*>(reinterpret_cast<char*>(lds) + eng.lds_bytes()) + B);
+  build_xcol(a, xCol, h + 1);
+  cx<T>* tile = inter + static_cast<long long>(zl) * a.interZStride + y0;
+  const int yl = min(B, a.Y - y0);
+  c2r_rows_to_lds(eng, lds, a, xCol, tile, yl, twh, twn);  // (a); ends with a barrier
+  const cx<T>* v = reinterpret_cast<const cx<T>*>(potential + (static_cast<long long>(zl) * a.Y + y0) * 2 * h);
+  scale_row_pairs<StreamV>(lds, v, yl * h, [&](int idx) {
+    const int b = idx / h;
+    return eng.out_at(b, idx - b * h);
+  }, [&](int idx) {
+    const int b = idx / h;
+    return fwd.in_at(b, idx - b * h);
+  });
+  __syncthreads();
+  fwd.lds_to_lds(lds, twh);  // (c); ends with a barrier
+  // (d): both outputs of a pair need the same two LDS values, and w^(h-k) =
+  // -conj(w^k); lanes run over rows first, so the column stores are contiguous
+  for (int idx = threadIdx.x; idx < B * (h / 2 + 1); idx += blockDim.x) {
+    const int b = idx % B, k = idx / B, m = h - k;
+    if (b >= yl) continue;
+    const int ck = xcol_of(a, xCol, k), cm = xcol_of(a, xCol, m);
+    if (ck < 0 && cm < 0) continue;
+    const cx<T> A = lds[fwd.out_at(b, k == h ? 0 : k)];
+    const cx<T> Bv = lds[fwd.out_at(b, m == h ? 0 : m)];
+    const cx<T> wk = twn[k];
+    if (ck >= 0) {
+      const cx<T> ym = conj(Bv);
+      const cx<T> e = scale(A + ym, T(0.5));
+      const cx<T> o = scale(rot<-1>(A - ym), T(0.5));
+      st_inter(&tile[inter_row(a, ck) + b], e + twm<-1>(o, wk));
+    }
+    if (cm >= 0 && m != k) {
+      const cx<T> ym = conj(A);
+      const cx<T> e = scale(Bv + ym, T(0.5));
+      const cx<T> o = scale(rot<-1>(Bv - ym), T(0.5));
+      st_inter(&tile[inter_row(a, cm) + b], e + twm<-1>(o, mk<T>(-wk.x, wk.y)));
+    }
+  }
+}
+
+// Engines whose batched packed-real density launch sums the bands of a full tile
+// in registers. A lane holds twice the values of x_density_kernel's sum (pairs),
+// which spilled on the fp64 h = 1024 shape (328 B per lane) and the fp32 h = 360
+// one (204 B): those update rho band by band, like partial tiles.
+template <class Eng>
+struct R2cDensityRegSum {
+  static constexpr bool value = true;
+};
+template <int S, bool LF, bool TwPre>
+struct R2cDensityRegSum<CtEng<double, 1024, S, LF, TwPre>> {
+  static constexpr bool value = false;
+};
+template <int S, bool LF, bool TwPre>
+struct R2cDensityRegSum<CtEng<float, 360, S, LF, TwPre>> {
+  static constexpr bool value = false;
+};
+// Engines whose batched packed-real density launch keeps the band loop inside the
+// workgroup (DensityBandLoop of the C2C stage). The fp32 h = 512 and h = 1024
+// shapes do not: the values the loop keeps live spilled with and without the
+// register sum (84 B and 292 B per lane without it). Their batches run one
+// single-band launch per band, in order on the stream.
+template <class Eng>
+struct R2cDensityBandLoop {
+  static constexpr bool value = true;
+};
+template <int S, bool LF, bool TwPre>
+struct R2cDensityBandLoop<CtEng<float, 512, S, LF, TwPre>> {
+  static constexpr bool value = false;
+};
+template <int S, bool LF, bool TwPre>
+struct R2cDensityBandLoop<CtEng<float, 1024, S, LF, TwPre>> {
+  static constexpr bool value = false;
+};
+
+// rho pair idx += w * {lds[src(idx)].x^2, lds[src(idx)].y^2} for idx in
+// [0, total): density_rows on packed-real rows (y.x = s[2m], y.y = s[2m+1]),
+// rho read and written as pairs. `rho` must be aligned to one pair.
+template <bool Stream, typename T, class Src>
+__device__ __forceinline__ void density_row_pairs(const cx<T>* lds, cx<T>* __restrict__ rho, T w, int total,
+                                                  Src src) {
+  for (int base = threadIdx.x; base < total; base += blockDim.x * kDensityUnroll) {
+    cx<T> r[kDensityUnroll];
+#pragma unroll
+    for (int u = 0; u < kDensityUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        if constexpr (Stream) r[u] = ld_stream(rho + idx);
+        else r[u] = rho[idx];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kDensityUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        const cx<T> y = lds[src(idx)];
+        const cx<T> v = mk<T>(fma(w, y.x * y.x, r[u].x), fma(w, y.y * y.y, r[u].y));
+        if constexpr (Stream) st_stream(rho + idx, v);
+        else rho[idx] = v;
+      }
+    }
+  }
+}
+
+// Fused density x stage (R2C, packed-real): step (a) of x_apply_r2c_kernel, then
+// rho[2m] += w y.x^2, rho[2m+1] += w y.y^2 on the workgroup's rows of rho. Tile
+// ownership, the band loop, the fixed sum order and the in-register sum of full
+// tiles are those of x_density_kernel; LDS and grid those of the C2R launch.
+template <class Eng, typename T, bool StreamRho, bool Batched>
+__global__ void __launch_bounds__(Eng::kBlock)
+    x_density_r2c_kernel(Eng eng, XArgs a, const cx<T>* __restrict__ inter, T* __restrict__ density,
+                         DensityWeights<T> weights, const cx<T>* __restrict__ twh,
+                         const cx<T>* __restrict__ twn) {
+  static_assert(!Eng::kBatchedCopy, "x density r2c: compile-time engines only");
+  SPFFT_LDS_DECL(T);
+  const int B = eng.lines();
+  const int h = eng.n();
+  int tx, ty;
+  block_tile(tx, ty);
+  const int zl = a.zBegin + ty;
+  const int y0 = tx * B;
+  int* xCol = reinterpret_cast<int*>(reinterpret_cast<cx<T>*>(reinterpret_cast<char*>(lds) + eng.lds_bytes()) + B);
+  build_xcol(a, xCol, h + 1);
+  const int yl = min(B, a.Y - y0);
+  cx<T>* rho = reinterpret_cast<cx<T>*>(density + (static_cast<long long>(zl) * a.Y + y0) * 2 * h);
+  auto fft = [&](const cx<T>* interM, const cx<T>* twhM, const cx<T>* twnM) {
+    c2r_rows_to_lds(eng, lds, a, xCol, interM + static_cast<long long>(zl) * a.interZStride + y0, yl, twhM, twnM);
+  };
+  auto row_at = [&](int idx) {
+    const int b = idx / h;
+    return eng.out_at(b, idx - b * h);
+  };
+  if constexpr (!Batched) {
+    fft(inter, twh, twn);
+    density_row_pairs<StreamRho>(lds, rho, weights.w[0], yl * h, row_at);
+  } else {
+    // the twiddle tables are pinned anew for every band (see x_density_kernel)
+    auto band_fft = [&](int m) {
+      const cx<T>* twhM = reinterpret_cast<const cx<T>*>(pin_uniform64(reinterpret_cast<long long>(twh)));
+      const cx<T>* twnM = reinterpret_cast<const cx<T>*>(pin_uniform64(reinterpret_cast<long long>(twn)));
+      if (m > 0) __syncthreads();  // the previous band's rows have been read
+      fft(static_cast<const cx<T>*>(a.batch.in[m]), twhM, twnM);
+    };
+    using F = typename Eng::F;
+    constexpr bool kEven = R2cDensityRegSum<Eng>::value && (F::B * Eng::kN) % F::NT == 0;
+    if (kEven && yl == F::B) {
+      constexpr int kIters = kEven ? F::B * Eng::kN / F::NT : 1;
+      cx<T> acc[kIters];
+#pragma unroll
+      for (int i = 0; i < kIters; ++i) acc[i] = czero<T>();
+      for (int m = 0; m < a.batch.count; ++m) {
+        band_fft(m);
+        const T w = weights.w[m];
+#pragma unroll
+        for (int i = 0; i < kIters; ++i) {
+          const cx<T> y = lds[row_at(static_cast<int>(threadIdx.x) + i * F::NT)];
+          acc[i] = mk<T>(fma(w, y.x * y.x, acc[i].x), fma(w, y.y * y.y, acc[i].y));
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < kIters; ++i) acc[i] = acc[i] + rho[static_cast<int>(threadIdx.x) + i * F::NT];
+#pragma unroll
+      for (int i = 0; i < kIters; ++i) rho[static_cast<int>(threadIdx.x) + i * F::NT] = acc[i];
+      return;
+    }
+    for (int m = 0; m < a.batch.count; ++m) {
+      band_fft(m);
+      density_row_pairs<StreamRho>(lds, rho, weights.w[m], yl * h, row_at);
+    }
+  }
+}
+
 // ------------------------------------------------------------ host helpers
 RtPlan make_rt_plan(int n, std::size_t elemBytes);
 

@@ -257,6 +257,82 @@ void launch_space_density(const void* space, T* density, T weight, long long cou
   gpu_check_launch("space_density", stream);
 }
 
+// Fused packed-real x stages (R2C, even n, compile-time half-length engine):
+// the line-fast backward engine of length n / 2 and the LDS and grid of the C2R
+// launch in launch_x_backward. x_r2c_fused_fits tells whether the engine of the
+// half-length n / 2 has these kernels (the launchers throw otherwise).
+template <typename T>
+bool x_r2c_fused_fits(int n) {
+  if (n < 4 || n % 2 != 0 || !has_ct_kernel(n / 2)) return false;
+  bool fits = false;
+  with_engine<T, +1, true>(n / 2, [&](auto eng, int, int, std::size_t) { fits = R2cFuseFits<decltype(eng)>::value; });
+  return fits;
+}
+
+template <typename T>
+void launch_x_apply_r2c(const XArgs& a, const T* potential, cx<T>* inter, bool plainPotential,
+                        const cx<T>* tw, const cx<T>* twHalf, hipStream_t stream) {
+  if (a.L <= a.zBegin || a.Y <= 0) return;
+  if (!twHalf || !has_ct_kernel(a.n / 2)) throw InternalError();
+  with_engine<T, +1, true>(a.n / 2, [&](auto eng, int threads, int lines, std::size_t lds) {
+    using E = decltype(eng);
+    if constexpr (R2cFuseFits<E>::value) {
+      auto fwd = forward_twin(eng);
+      using F = decltype(fwd);
+      auto k = plainPotential ? x_apply_r2c_kernel<E, F, T, false> : x_apply_r2c_kernel<E, F, T, true>;
+      const std::size_t ldsTotal =
+          lds + std::size_t(lines) * sizeof(cx<T>) + std::size_t(a.n / 2 + 1) * sizeof(int) + 16;
+      prepare_kernel(k, ldsTotal);
+      hipLaunchKernelGGL(k, dim3(ceil_div(a.Y, lines), a.L - a.zBegin, batch_dim(a.batch)), dim3(threads), ldsTotal,
+                         stream, eng, fwd, a, potential, inter, twHalf, tw);
+      gpu_check_launch("x_apply_r2c", stream);
+    } else {
+      throw InternalError();
+    }
+  });
+}
+
+template <typename T>
+void launch_x_density_r2c(const XArgs& a, const cx<T>* inter, T* density, const T* weights, const cx<T>* tw,
+                          const cx<T>* twHalf, hipStream_t stream) {
+  if (a.L <= a.zBegin || a.Y <= 0) return;
+  if (!twHalf || !has_ct_kernel(a.n / 2)) throw InternalError();
+  const int bands = a.batch.count > 1 ? a.batch.count : 1;
+  DensityWeights<T> w{};
+  for (int m = 0; m < bands && m < kMaxBatch; ++m) w.w[m] = weights[m];
+  with_engine<T, +1, true>(a.n / 2, [&](auto eng, int threads, int lines, std::size_t lds) {
+    using E = decltype(eng);
+    if constexpr (R2cFuseFits<E>::value) {
+      const std::size_t ldsTotal =
+          lds + std::size_t(lines) * sizeof(cx<T>) + std::size_t(a.n / 2 + 1) * sizeof(int) + 16;
+      const dim3 grid(ceil_div(a.Y, lines), a.L - a.zBegin, 1);
+      if constexpr (R2cDensityBandLoop<E>::value) {
+        if (bands > 1) {
+          // the bands of a batch revisit the tile of rho: default-policy accesses
+          auto k = x_density_r2c_kernel<E, T, false, true>;
+          prepare_kernel(k, ldsTotal);
+          hipLaunchKernelGGL(k, grid, dim3(threads), ldsTotal, stream, eng, a, inter, density, w, twHalf, tw);
+          gpu_check_launch("x_density_r2c", stream);
+          return;
+        }
+      }
+      auto single = x_density_r2c_kernel<E, T, SPFFT_DENSITY_STREAM_RHO != 0, false>;
+      prepare_kernel(single, ldsTotal);
+      XArgs one = a;
+      one.batch.count = 0;
+      for (int m = 0; m < bands; ++m) {
+        DensityWeights<T> wm{};
+        wm.w[0] = w.w[m];
+        hipLaunchKernelGGL(single, grid, dim3(threads), ldsTotal, stream, eng, one,
+                           bands > 1 ? static_cast<const cx<T>*>(a.batch.in[m]) : inter, density, wm, twHalf, tw);
+        gpu_check_launch("x_density_r2c", stream);
+      }
+    } else {
+      throw InternalError();
+    }
+  });
+}
+
 // Cache policy of the fused pair operator's space-array accesses (a, b in the
 // forward x stage; a, acc in the backward x stage): streaming (1) or plain (0).
 #ifndef SPFFT_FOCK_STREAM

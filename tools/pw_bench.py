@@ -11,7 +11,11 @@ composition of backward and torch passes; --op hartree times
 PlaneWaveModel.hartree_potential, one apply_reciprocal per call, against its
 composition forward, K(G) multiply, backward in alternating rounds of one
 process, and prints the GPU stage times of both and the modelled bytes of the two
-z stages; with --r2c on an R2C transform; --op fock times one exchange pair,
+z stages; with --r2c on an R2C transform; --op local / density with --r2c time
+--transforms bands per call on R2C transforms over the hermitian half of the sphere,
+three variants in alternating rounds of one process: multi_transform_backward, torch
+passes and multi_transform_forward; the library's composed path (transforms created under
+SPFFT_R2C_FUSE=0); the fused call; --op fock times one exchange pair,
 accumulate_fock on the model's pair-density transform (the sphere |G|^2/2 <= 4
 ecut) against torch product, apply_reciprocal, torch addcmul_, with the same
 protocol and the modelled bytes of both; with --transforms T > 1 it times T
@@ -55,7 +59,8 @@ def main():
                     help="FFT grid N^3 instead of the density grid of the cutoff (the cutoff "
                          "sphere may then reach N/2, the transforms' own minimum grid)")
     ap.add_argument("--r2c", action="store_true",
-                    help="--op hartree on an R2C transform (hermitian half of the sphere)")
+                    help="--op hartree, local, density, gradient, divergence on R2C transforms "
+                         "(hermitian half of the sphere)")
     a = ap.parse_args()
     import torch
 
@@ -91,6 +96,9 @@ def main():
     v_r = torch.rand((nz, ny, nx), dtype=torch.float64, device=dev, generator=g)
     if a.op == "hartree":
         hartree(a, basis, model, v_r)  # (a real field stands in for rho)
+        return
+    if a.r2c:
+        r2c_ops(a, basis, v_r)
         return
     if a.op == "density":
         weights = [1.0 + 0.01 * b for b in range(a.bands)]
@@ -132,6 +140,123 @@ def _gpu_stage_medians(tree):
             for st in d["sub-timings"]:
                 out[d["identifier"] + "/" + st["identifier"]] = st["median"]
     return out
+
+
+def _hermitian_half(basis):
+    """The half of the model's sphere an R2C transform takes: x >= 0, and of the x = 0
+    plane y >= 0 (of the (0,0) stick z >= 0)."""
+    import numpy as np
+    idx = basis.indices
+    keep = (idx[:, 0] > 0) | ((idx[:, 0] == 0) & ((idx[:, 1] > 0) |
+                                                 ((idx[:, 1] == 0) & (idx[:, 2] >= 0))))
+    return np.ascontiguousarray(idx[keep])
+
+
+def r2c_ops(a, basis, v_r):
+    """--op local / density --r2c: B = --transforms bands per call on R2C transforms over
+    the hermitian half of the sphere. Variants, alternating in one process (medians over the
+    rounds): "torch" multi_transform_backward, torch passes over the real space domains,
+    (multi_transform_forward); "composed" the library's composed path on transforms created
+    under SPFFT_R2C_FUSE=0; "fused" the call on the default plan. Then the GPU stage medians
+    of the single-transform call of each library variant, and the byte model of the x part
+    (columns c = nx/2+1 of ny rows per plane, 16 B per element, real rows of nx * 8 B)."""
+    import numpy as np
+    import torch
+
+    import spfft_amd as sp
+    nx, ny, nz = basis.fft_dims
+    idx = _hermitian_half(basis)
+    B = max(1, a.transforms)
+
+    def make(env):
+        saved = {k: os.environ.get(k) for k in env}
+        os.environ.update(env)
+        try:
+            ts = []
+            for _ in range(B):
+                grid = sp.Grid(nx, ny, nz, nx * ny, sp.ProcessingUnit.GPU, 1)
+                ts.append(grid.create_transform(sp.ProcessingUnit.GPU, sp.TransformType.R2C,
+                                                nx, ny, nz, nz, idx))
+            return ts
+        finally:
+            for k, v in saved.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
+
+    fused_ts, composed_ts = make({}), make({"SPFFT_R2C_FUSE": "0"})
+    # hermitian-consistent values: the forward transform of real fields
+    g = torch.Generator(device="cuda")
+    g.manual_seed(6)
+    psi = []
+    for _ in range(B):
+        f = torch.randn((nz, ny, nx), dtype=torch.float64, device="cuda", generator=g)
+        psi.append(fused_ts[0].forward(space=f, scaling=sp.Scaling.FULL).clone())
+    weights = [1.0 + 0.01 * b for b in range(B)]
+    rho = torch.zeros((nz, ny, nx), dtype=torch.float64, device="cuda")
+    pots = [v_r] * B
+    density = a.op == "density"
+
+    def call(variant):
+        if variant == "torch":
+            spaces = sp.multi_transform_backward(fused_ts, psi)
+            if density:
+                for s, w in zip(spaces, weights):
+                    rho.addcmul_(s, s, value=w)
+                return rho
+            for s in spaces:
+                s.mul_(v_r)
+            return sp.multi_transform_forward(fused_ts)
+        ts = fused_ts if variant == "fused" else composed_ts
+        if density:
+            return sp.multi_transform_accumulate_density(ts, psi, weights, rho)
+        return sp.multi_transform_apply_local(ts, psi, pots)
+
+    variants = ("torch", "composed", "fused")
+    rounds, calls = max(3, a.reps), 10
+    times = {v: [] for v in variants}
+    for v in variants:
+        call(v)
+    for _ in range(rounds):
+        for v in variants:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                call(v)
+            torch.cuda.synchronize()
+            times[v].append((time.perf_counter() - t0) / calls)
+    med = {v: sorted(x)[len(x) // 2] for v, x in times.items()}
+    stages = {}
+    for v, ts in (("composed", composed_ts), ("fused", fused_ts)):
+        sp.timing_reset()
+        sp.timing_enable(True)
+        try:
+            for _ in range(calls):
+                if density:
+                    ts[0].accumulate_density(psi[0], 1.0, rho)
+                else:
+                    ts[0].apply_local(psi[0], v_r)
+            ts[0].synchronize()
+            torch.cuda.synchronize()
+            stages[v] = _gpu_stage_medians(sp.timing_json())
+        finally:
+            sp.timing_enable(False)
+    inter, real = (nx // 2 + 1) * ny * nz * 16, nx * ny * nz * 8
+    if density:
+        model = {"composed": inter + real + 3 * real, "fused": inter + 2 * real}
+    else:
+        model = {"composed": (inter + real) + 3 * real + (real + inter), "fused": 2 * inter + real}
+    best = min(med["torch"], med["composed"])
+    print(json.dumps({"workload": "plane-wave " + ("density" if density else "H_loc psi"), "type": "r2c",
+                      "fft_dims": list(basis.fft_dims), "num_values": int(len(idx)), "bands_per_call": B,
+                      "fused": bool(fused_ts[0].density_fused if density else fused_ts[0].apply_local_fused),
+                      "us_per_call": {v: 1e6 * x for v, x in med.items()},
+                      "range_us": {v: [1e6 * min(x), 1e6 * max(x)] for v, x in times.items()},
+                      "ratio_best_other_over_fused": best / med["fused"],
+                      "gpu_stage_median_s": stages,
+                      "model_x_bytes": model,
+                      "model_x_ratio": model["composed"] / model["fused"]}), flush=True)
 
 
 def hartree(a, basis, model, rho):
