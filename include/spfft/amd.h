@@ -252,11 +252,20 @@ SPFFT_EXPORT SpfftError spfft_amd_float_transform_reciprocal_fused(SpfftFloatTra
  * pointers; host arrays of a GPU transform are staged on its stream. a == b is
  * allowed, acc overlapping a or b is undefined; a and b are not modified.
  * scaling is SPFFT_NO_SCALING or SPFFT_FULL_SCALING. After the call the contents
- * of the space domain are unspecified: fused plans (GPU C2C transforms whose x
- * lines fit one workgroup) form the pair density in the forward x stage's loads
- * and accumulate from the backward x stage's LDS, never form the space domain
- * and leave it untouched; other plans (R2C, long x lines, host) pass through
- * it. The z stage is the one of apply_reciprocal. Collective on distributed
+ * of the space domain are unspecified: fused plans form the pair density in the
+ * forward x stage's loads and accumulate from the backward x stage's LDS, never
+ * form the space domain and leave it untouched; other plans pass through it.
+ * Fused are GPU C2C transforms whose x lines fit one workgroup
+ * (spfft_amd_transform_fock_fused) and GPU R2C transforms with even dimX whose
+ * half-length dimX / 2 has a compile-time kernel, on the packed-real x stages
+ * (spfft_amd_transform_fock_r2c_fused; the plans named at
+ * spfft_amd_transform_apply_local, SPFFT_R2C_FUSE=0 or SPFFT_R2C_PACKED=0 at
+ * creation keeps them composed). Odd dimX, other half-lengths, long x lines and
+ * host transforms run composed. On a fused R2C plan a, b and acc are accessed
+ * as pairs of elements: where a device array is not aligned to 2 *
+ * sizeof(element), the half of the call that uses it (forward: a, b; backward:
+ * a, acc) runs composed and passes through the space domain.
+ * The z stage is the one of apply_reciprocal. Collective on distributed
  * grids. A null a, b or acc with local planes, or a null kernel with local
  * values, is SPFFT_INVALID_PARAMETER_ERROR; the transform stays usable. */
 SPFFT_EXPORT SpfftError spfft_amd_transform_accumulate_fock(SpfftTransform t, const double* a,
@@ -279,7 +288,9 @@ SPFFT_EXPORT SpfftError spfft_amd_float_transform_accumulate_fock(SpfftFloatTran
  * i, all real or all interleaved complex (kernelIsComplex); the pointers may
  * all be equal. One scaling for the call; there is no values output. All
  * pointers are host or device pointers. Identical plans on one GPU with fused
- * x and z stages and device pointers share one launch per stage, and the
+ * x and z stages (C2C, or the packed-real R2C pair stages; an R2C member whose
+ * a[i], b[i] or acc is not aligned to 2 * sizeof(element) runs per transform)
+ * and device pointers share one launch per stage, and the
  * workgroup that owns a tile of acc adds the members' updates in list order
  * (SPFFT_BATCH); everything else runs per transform with the phases
  * interleaved. Every update of acc is ordered behind the previous one: the sum
@@ -297,9 +308,16 @@ SPFFT_EXPORT SpfftError spfft_amd_float_multi_transform_accumulate_fock(
     int n, SpfftFloatTransform* transforms, const float* const* a, const float* const* b,
     const float* const* kernels, int kernelIsComplex, const float* weights, float* acc,
     SpfftScalingType scaling);
-/* *fused = 1 if the plan runs the fused pair x stages on the GPU, else 0. */
+/* *fused = 1 if the plan runs the fused C2C pair x stages on the GPU, else 0
+ * (0 on every R2C plan: see spfft_amd_transform_fock_r2c_fused). */
 SPFFT_EXPORT SpfftError spfft_amd_transform_fock_fused(SpfftTransform t, int* fused);
 SPFFT_EXPORT SpfftError spfft_amd_float_transform_fock_fused(SpfftFloatTransform t, int* fused);
+/* *fused = 1 if the plan runs the packed-real pair x stages (GPU R2C, even dimX,
+ * compile-time half-length kernel), else 0: C2C, host, odd dimX, run-time
+ * half-lengths, long x lines, SPFFT_R2C_FUSE=0 or SPFFT_R2C_PACKED=0 at
+ * creation. A null fused is SPFFT_INVALID_PARAMETER_ERROR. */
+SPFFT_EXPORT SpfftError spfft_amd_transform_fock_r2c_fused(SpfftTransform t, int* fused);
+SPFFT_EXPORT SpfftError spfft_amd_float_transform_fock_r2c_fused(SpfftFloatTransform t, int* fused);
 
 /* Reciprocal fan-out (gradient-like): one forward transform feeds n backward
  * transforms,

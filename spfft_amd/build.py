@@ -44,7 +44,7 @@ def build(clean: bool = False, jobs: int | None = None, build_type: str = "Relea
         _install(so, os.path.join(NATIVE_DIR, os.path.basename(so)))
     for exe in ("spfft_bench", "spfft_native_tests", "spfft_mpi_tests", "spfft_apply_local_test",
                 "spfft_density_test", "spfft_reciprocal_test", "spfft_fock_test",
-                "spfft_fock_multi_test", "spfft_reciprocal_fan_test",
+                "spfft_fock_multi_test", "spfft_fock_r2c_test", "spfft_reciprocal_fan_test",
                 "spfft_values_fan_test", "spfft_spinor_test",
                 "example_c", "example_cpp", "example_f90"):
         src = os.path.join(BUILD_DIR, exe)

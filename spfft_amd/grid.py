@@ -588,8 +588,11 @@ class _TransformBase:
         array; `acc` is updated in place, never copied, and must not overlap them.
         `kernel` and `values` are as in apply_reciprocal; `values` receives the scaled
         forward values c(G) of the pair density. The contents of the space domain are
-        unspecified afterwards; fused plans (see fock_fused) never form it and leave it
-        untouched. Returns `acc`."""
+        unspecified afterwards; fused plans (see fock_fused for C2C and fock_r2c_fused for
+        R2C) never form it and leave it untouched. On a fused R2C plan `a`, `b` and `acc`
+        are accessed as pairs of elements: a device array not aligned to two elements makes
+        the half of the call that uses it run composed, through the space domain. Returns
+        `acc`."""
         shape = self.space_domain_shape()
         real = self.type == TransformType.R2C
         aptr, akeep = _space_array_ptr(a, self._prec, shape, real, "a", False)
@@ -619,13 +622,26 @@ class _TransformBase:
 
     @property
     def fock_fused(self) -> bool:
-        """True if accumulate_fock runs the fused pair x stages (GPU, C2C, x lines of one
-        workgroup); its z stage follows reciprocal_fused."""
+        """True if accumulate_fock runs the fused C2C pair x stages (GPU, C2C, x lines of one
+        workgroup); its z stage follows reciprocal_fused. False on every R2C plan: see
+        fock_r2c_fused."""
         c = self._cache.get("fock_fused")
         if c is None:
             v = ctypes.c_int()
             _check(self._prec.amd_fn("transform_fock_fused")(self._h, ctypes.byref(v)))
             c = self._cache["fock_fused"] = bool(v.value)
+        return c
+
+    @property
+    def fock_r2c_fused(self) -> bool:
+        """True if accumulate_fock runs the packed-real pair x stages (GPU, R2C with even
+        dim_x whose half-length has a compile-time kernel; SPFFT_R2C_FUSE=0 or
+        SPFFT_R2C_PACKED=0 at creation keeps the composed path)."""
+        c = self._cache.get("fock_r2c_fused")
+        if c is None:
+            v = ctypes.c_int()
+            _check(self._prec.amd_fn("transform_fock_r2c_fused")(self._h, ctypes.byref(v)))
+            c = self._cache["fock_r2c_fused"] = bool(v.value)
         return c
 
     # --------------------------------------------------- streams / step API
@@ -805,8 +821,10 @@ def multi_transform_accumulate_fock(transforms, a, b, kernel, weights, acc, scal
     `a` and `b` hold one array per transform as in accumulate_fock (`b[i]` may be the same
     array for every i, and may be `a[i]`); `kernel` is one array or tensor shared by all
     transforms or a sequence of one per transform, all real or all complex. Identical
-    fused plans on one GPU share one launch per stage, and their updates of `acc` run
-    inside one workgroup per tile; the sum order is fixed by the call. Returns `acc`."""
+    fused plans on one GPU (fock_fused, or fock_r2c_fused on R2C) share one launch per
+    stage, and their updates of `acc` run inside one workgroup per tile; the sum order is
+    fixed by the call. An R2C member whose `a[i]`, `b[i]` or `acc` is not aligned to two
+    elements runs per transform instead. Returns `acc`."""
     n, prec, arr = _multi(transforms)
     if len(a) != n or len(b) != n or len(weights) != n:
         raise ValueError("one a, one b and one weight per transform")

@@ -133,6 +133,7 @@ def _prototypes(lib):
     for pre, real in (("spfft_amd_", ctypes.c_double), ("spfft_amd_float_", ctypes.c_float)):
         sig[pre + "transform_accumulate_fock"] = [V, D, D, D, I, real, D, D, I]
         sig[pre + "transform_fock_fused"] = [V, c_int_p]
+        sig[pre + "transform_fock_r2c_fused"] = [V, c_int_p]
         sig[pre + "multi_transform_accumulate_fock"] = [I, c_void_pp, c_void_pp, c_void_pp,
                                                         c_void_pp, I, D, D, I]
     for pre in ("spfft_amd_", "spfft_amd_float_"):

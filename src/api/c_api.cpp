@@ -722,6 +722,15 @@ SpfftError spfft_amd_float_transform_fock_fused(SpfftFloatTransform t, int* fuse
   return with_handle<TransformFloat>(
       t, [&](TransformFloat& x) { *fused = x.impl()->fock_fused() ? 1 : 0; });
 }
+SpfftError spfft_amd_transform_fock_r2c_fused(SpfftTransform t, int* fused) {
+  if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
+  return with_handle<Transform>(t, [&](Transform& x) { *fused = x.impl()->fock_r2c_fused() ? 1 : 0; });
+}
+SpfftError spfft_amd_float_transform_fock_r2c_fused(SpfftFloatTransform t, int* fused) {
+  if (!fused) return SPFFT_INVALID_PARAMETER_ERROR;
+  return with_handle<TransformFloat>(
+      t, [&](TransformFloat& x) { *fused = x.impl()->fock_r2c_fused() ? 1 : 0; });
+}
 
 SpfftError spfft_amd_multi_transform_reciprocal_fan_out(int n, SpfftTransform* transforms,
                                                         SpfftProcessingUnitType location,

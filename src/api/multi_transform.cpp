@@ -305,7 +305,11 @@ void multi_accumulate_fock(const std::vector<TransformImpl<T>*>& ts, const T* co
       ts,
       [&](int i) {
         const IndexPlan& p = ts[i]->plan();
-        return ts[i]->fock_fused() && ts[i]->reciprocal_fused() && deviceAcc &&
+        // (a packed-real R2C pair plan reads a, b and acc as pairs: members with a
+        // misaligned array take the per-transform path, which runs them composed)
+        const bool pairs = ts[i]->fock_r2c_fused() && ts[i]->gpu()->fock_pairs_aligned(a[i]) &&
+                           ts[i]->gpu()->fock_pairs_aligned(b[i]) && ts[i]->gpu()->fock_pairs_aligned(acc);
+        return (ts[i]->fock_fused() || pairs) && ts[i]->reciprocal_fused() && deviceAcc &&
                (p.local_planes() == 0 || (is_device_pointer(a[i]) && is_device_pointer(b[i]))) &&
                (p.numLocalElements == 0 || is_device_pointer(kernels[i]));
       },

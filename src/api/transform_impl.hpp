@@ -72,6 +72,7 @@ public:
   void accumulate_fock(const T* a, const T* b, const T* kernel, bool complexKernel, T weight, T* acc,
                        T* values, SpfftScalingType scaling);
   bool fock_fused() const { return gpu_ && gpu_->fock_fused(); }
+  bool fock_r2c_fused() const { return gpu_ && gpu_->fock_r2c_fused(); }
   // the stages of accumulate_fock around the two exchanges (multi-transform
   // interleaving): fock_forward_xy, forward_exchange, reciprocal_z,
   // backward_exchange, fock_backward_xy

@@ -129,6 +129,9 @@ GpuExecutor<T>::GpuExecutor(std::shared_ptr<GridImpl<T>> grid,
   r2cFused_ = twXh_ && !longX_ && dev::has_ct_kernel(p.dimX / 2) && dev::x_r2c_fused_fits<T>(p.dimX) &&
               env_int("SPFFT_R2C_FUSE", 1, 0, 1) != 0;
   if (r2cFused_) applyFused_ = densityFused_ = true;
+  // accumulate_fock on such a plan runs the packed-real pair x stages where both
+  // engines of the half-length have them; fockFused_ stays the C2C flag
+  fockR2cFused_ = r2cFused_ && dev::x_r2c_fock_fits<T>(p.dimX);
   upload(twY_, make_twiddles<T>(p.dimY));
   upload(twZ_, make_twiddles<T>(p.dimZ));
 
@@ -251,7 +254,7 @@ void GpuExecutor<T>::log_plan() const {
                describe(longX_, lpX_, twXh_ ? p.dimX / 2 : p.dimX, true).c_str(),
                twXh_ ? " packed-real" : "", interPlanes_, applyFused_ ? "fused" : "unfused",
                densityFused_ ? "fused" : "composed", reciprocalFused_ ? "fused" : "composed",
-               fockFused_ ? "fused" : "composed", layout_.buffered ? "buffered" : "compact",
+               fockFused_ || fockR2cFused_ ? "fused" : "composed", layout_.buffered ? "buffered" : "compact",
                floatExchange_ ? "-float" : "", plane.c_str(), exchChunks_, stickBlocks_, bwdSteps_.size(),
                fwdSteps_.size(), chunkModel_ / 1e6, peerWrites_ ? 1 : 0, peerOffsetRange_[0],
                peerOffsetRange_[1], GpuStream::live(), values_fan_fused() ? "fused" : "composed");
@@ -1544,10 +1547,13 @@ void GpuExecutor<T>::accumulate_density_xy(T* density, T weight, GpuExecutor* af
 // ------------------------------------------------- exchange (Fock) pair operator
 // accumulate_fock = fock_forward_xy, forward_exchange, reciprocal_z,
 // backward_exchange, fock_backward_xy (TransformImpl::accumulate_fock). Fused
-// plans (C2C, x lines of one workgroup) run the loops of forward_xy and
-// backward_xy with the pair x stages and never form the space domain; other
-// plans pass through it with one pointwise kernel at either end. Host a, b and
-// acc are staged through device buffers on the stream.
+// plans (C2C with x lines of one workgroup: fockFused_; R2C on the packed-real
+// pair stages: fockR2cFused_) run the loops of forward_xy and backward_xy with
+// the pair x stages and never form the space domain; other plans pass through
+// it with one pointwise kernel at either end. On a fused R2C plan a forward half
+// whose a or b, and a backward half whose a or acc, cannot be accessed as pairs
+// runs composed as well. Host a, b and acc are staged through device buffers
+// (which are aligned) on the stream.
 template <typename T>
 std::size_t GpuExecutor<T>::space_elements() const {
   const IndexPlan& p = *plan_;
@@ -1573,7 +1579,10 @@ void GpuExecutor<T>::fock_forward_xy(const T* a, const T* b) {
   };
   const T* da = device(a, fockA_);
   const T* db = b == a ? da : device(b, fockB_);
-  if (!fockFused_) {
+  // (the two halves of a call decide independently: a composed half passes
+  // through the space domain, and either half hands on the same intermediate)
+  const bool pairR2c = fockR2cFused_ && fock_pairs_aligned(da) && fock_pairs_aligned(db);
+  if (!fockFused_ && !pairR2c) {
     dev::launch_space_pair<T>(grid_->device_slot(GridImpl<T>::kSpace), da, db, static_cast<long long>(count),
                               real, stream_);
     stage_mark("forward", "pair");
@@ -1583,8 +1592,11 @@ void GpuExecutor<T>::fock_forward_xy(const T* a, const T* b) {
   StageEnd stageEnd{this, "forward", "x_pair+y"};
   poison(false);
   forward_xy_ranges([&](const dev::XArgs& xa, cx<T>* out) {
-    dev::launch_x_forward_pair<T>(xa, reinterpret_cast<const cx<T>*>(da), reinterpret_cast<const cx<T>*>(db), out,
-                                  twX_->data<cx<T>>(), stream_);
+    if (pairR2c)
+      dev::launch_x_forward_pair_r2c<T>(xa, da, db, out, twX_->data<cx<T>>(), twXh_->data<cx<T>>(), stream_);
+    else
+      dev::launch_x_forward_pair<T>(xa, reinterpret_cast<const cx<T>*>(da), reinterpret_cast<const cx<T>*>(db), out,
+                                    twX_->data<cx<T>>(), stream_);
   });
 }
 
@@ -1608,7 +1620,8 @@ void GpuExecutor<T>::fock_backward_xy(const T* a, T* acc, T weight, GpuExecutor*
     after = nullptr;
     gpu_check(hipMemcpyAsync(dacc, acc, bytes, hipMemcpyHostToDevice, stream_), "hipMemcpyAsync");
   }
-  if (!fockFused_) {
+  const bool pairR2c = fockR2cFused_ && fock_pairs_aligned(da) && fock_pairs_aligned(dacc);
+  if (!fockFused_ && !pairR2c) {
     backward_xy(SPFFT_PU_GPU);
     order_after_density(after);
     dev::launch_space_fock<T>(grid_->device_slot(GridImpl<T>::kSpace), da, dacc, weight,
@@ -1619,8 +1632,12 @@ void GpuExecutor<T>::fock_backward_xy(const T* a, T* acc, T weight, GpuExecutor*
     backward_yx_ranges([&](const dev::XArgs& xa, cx<T>* tile) {
       order_after_density(after);  // (once: the stream stays behind it)
       after = nullptr;
-      dev::launch_x_backward_fock<T>(xa, tile, reinterpret_cast<const cx<T>*>(da), reinterpret_cast<cx<T>*>(dacc),
-                                     weight, twX_->data<cx<T>>(), stream_);
+      if (pairR2c)
+        dev::launch_x_backward_fock_r2c<T>(xa, tile, da, dacc, weight, twX_->data<cx<T>>(), twXh_->data<cx<T>>(),
+                                           stream_);
+      else
+        dev::launch_x_backward_fock<T>(xa, tile, reinterpret_cast<const cx<T>*>(da), reinterpret_cast<cx<T>*>(dacc),
+                                       weight, twX_->data<cx<T>>(), stream_);
     });
   }
   if (staged) gpu_check(hipMemcpyAsync(acc, dacc, bytes, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync");
@@ -1953,7 +1970,9 @@ void GpuExecutor<T>::accumulate_density_batch(const std::vector<GpuExecutor*>& e
 // (in place on the members' stick sides), y backward, then one accumulating x
 // launch whose workgroups loop over the members for their tile of acc (the
 // members share acc, so they are not spread over the grid). A b shared by the
-// whole batch is read with the default cache policy.
+// whole batch is read with the default cache policy. The members are all C2C
+// pair plans or all packed-real R2C pair plans (the batch key holds the type);
+// the R2C launches need a, b and acc aligned to one pair.
 template <typename T>
 void GpuExecutor<T>::accumulate_fock_batch(const std::vector<GpuExecutor*>& ex, const std::vector<const T*>& a,
                                            const std::vector<const T*>& b,
@@ -1968,8 +1987,10 @@ void GpuExecutor<T>::accumulate_fock_batch(const std::vector<GpuExecutor*>& ex, 
   GpuExecutor* l = ex[0];
   DeviceGuard guard(l->deviceId_);
   for (GpuExecutor* e : ex)
-    if (!e->batchable() || !e->fockFused_ || !e->reciprocalFused_ || e->batchKey_ != l->batchKey_)
+    if (!e->batchable() || !(e->fockFused_ || e->fockR2cFused_) || e->fockR2cFused_ != l->fockR2cFused_ ||
+        !e->reciprocalFused_ || e->batchKey_ != l->batchKey_)
       throw InternalError();
+  const bool r2c = l->fockR2cFused_;
   const IndexPlan& p = *l->plan_;
   const bool planes = p.local_planes() > 0;
   if (planes && (!acc || !is_device_pointer(acc))) throw InvalidParameterError();
@@ -1986,6 +2007,8 @@ void GpuExecutor<T>::accumulate_fock_batch(const std::vector<GpuExecutor*>& ex, 
       throw InvalidParameterError();
     if (p.numLocalElements > 0 && (!kernels[i] || !is_device_pointer(kernels[i])))
       throw InvalidParameterError();
+    if (r2c && !(l->fock_pairs_aligned(a[i]) && l->fock_pairs_aligned(b[i]) && l->fock_pairs_aligned(acc)))
+      throw InternalError();
     shared = shared && b[i] == b[0];
     pa[i] = reinterpret_cast<const cx<T>*>(a[i]);
     pb[i] = reinterpret_cast<const cx<T>*>(b[i]);
@@ -2009,7 +2032,10 @@ void GpuExecutor<T>::accumulate_fock_batch(const std::vector<GpuExecutor*>& ex, 
   auto xa = l->xargs();
   hipStream_t s = l->stream_;
   xa.batch = xf;
-  dev::launch_x_forward_pair_batch<T>(xa, pb.data(), shared, l->twX_->data<cx<T>>(), s);
+  if (r2c)
+    dev::launch_x_forward_pair_r2c_batch<T>(xa, b.data(), shared, l->twX_->data<cx<T>>(), l->twXh_->data<cx<T>>(), s);
+  else
+    dev::launch_x_forward_pair_batch<T>(xa, pb.data(), shared, l->twX_->data<cx<T>>(), s);
   ya.batch = yf;
   dev::launch_y_forward<T, cx<T>>(ya, static_cast<const cx<T>*>(yf.in[0]), static_cast<cx<T>*>(yf.out[0]),
                                   l->twY_->data<cx<T>>(), s);
@@ -2022,8 +2048,12 @@ void GpuExecutor<T>::accumulate_fock_batch(const std::vector<GpuExecutor*>& ex, 
                                    l->twY_->data<cx<T>>(), s);
   l->order_after_density(after);
   xa.batch = xb;
-  dev::launch_x_backward_fock_batch<T>(xa, pa.data(), weights.data(), reinterpret_cast<cx<T>*>(acc),
-                                       l->twX_->data<cx<T>>(), s);
+  if (r2c)
+    dev::launch_x_backward_fock_r2c_batch<T>(xa, a.data(), weights.data(), acc, l->twX_->data<cx<T>>(),
+                                             l->twXh_->data<cx<T>>(), s);
+  else
+    dev::launch_x_backward_fock_batch<T>(xa, pa.data(), weights.data(), reinterpret_cast<cx<T>*>(acc),
+                                         l->twX_->data<cx<T>>(), s);
   batch_release(ex);
 }
 

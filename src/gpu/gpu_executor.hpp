@@ -126,6 +126,14 @@ public:
   void fock_forward_xy(const T* a, const T* b);
   void fock_backward_xy(const T* a, T* acc, T weight, GpuExecutor* after = nullptr);
   bool fock_fused() const { return fockFused_; }
+  // R2C plans that run the packed-real pair x stages instead (fock_fused() stays
+  // false on them). Those stages access a, b and acc as pairs of real elements:
+  // fock_pairs_aligned is true unless this is such a plan and p is not aligned
+  // to 2 * sizeof(T); a half of a call with a misaligned array runs composed.
+  bool fock_r2c_fused() const { return fockR2cFused_; }
+  bool fock_pairs_aligned(const void* p) const {
+    return !fockR2cFused_ || reinterpret_cast<std::uintptr_t>(p) % (2 * sizeof(T)) == 0;
+  }
   // batchable() plans with fused x and z stages and equal keys into one acc:
   // one launch per stage on the leader's stream, the accumulating x workgroups
   // loop over the members in order (device pointers)
@@ -266,7 +274,8 @@ private:
   std::unique_ptr<DeviceBuffer> fanBuf_[4];
   mutable int spinorFits_ = -1;  // x line region fits the LDS twice (-1: not yet asked)
   std::unique_ptr<DeviceBuffer> spinorBuf_;  // stages four host potential / density arrays
-  bool fockFused_ = false;
+  bool fockFused_ = false;     // C2C pair x stages
+  bool fockR2cFused_ = false;  // packed-real pair x stages of a fused R2C plan
   std::unique_ptr<DeviceBuffer> fockA_, fockB_, fockAcc_;  // stage host a, b, acc
   std::size_t space_elements() const;  // elements of the local space domain
   struct GraphEntry {

@@ -219,6 +219,28 @@ void launch_z_reciprocal_batch(const ZArgs& a, bool complexKernel, T scale, cons
 template <typename T>
 void launch_x_backward_fock_batch(const XArgs& a, const cx<T>* const* pa, const T* weights, cx<T>* acc,
                                   const cx<T>* tw, hipStream_t stream);
+// Pair operator on the packed-real rows of R2C transforms with even n whose
+// half-length n / 2 has a compile-time engine (x_r2c_fock_fits; the launchers
+// throw otherwise): a, b and acc are real arrays [z][y][x], read and written as
+// pairs (s[2m], s[2m+1]), so their pointers must be aligned to 2 * sizeof(T).
+// Forward: the packed-real x stage of forward_xy whose rows are a * b. Backward:
+// the packed-real x stage of backward_xy whose result u is not stored: acc +=
+// weight * a * u. `tw` / `twHalf` as launch_x_backward. The batched launches as
+// their C2C counterparts (batch.in[m] of the forward launch is member m's a).
+template <typename T>
+bool x_r2c_fock_fits(int n);
+template <typename T>
+void launch_x_forward_pair_r2c(const XArgs& a, const T* pa, const T* pb, cx<T>* inter, const cx<T>* tw,
+                               const cx<T>* twHalf, hipStream_t stream);
+template <typename T>
+void launch_x_backward_fock_r2c(const XArgs& a, const cx<T>* inter, const T* pa, T* acc, T weight, const cx<T>* tw,
+                                const cx<T>* twHalf, hipStream_t stream);
+template <typename T>
+void launch_x_forward_pair_r2c_batch(const XArgs& a, const T* const* pb, bool plainLoads, const cx<T>* tw,
+                                     const cx<T>* twHalf, hipStream_t stream);
+template <typename T>
+void launch_x_backward_fock_r2c_batch(const XArgs& a, const T* const* pa, const T* weights, T* acc,
+                                      const cx<T>* tw, const cx<T>* twHalf, hipStream_t stream);
 // Reciprocal fan-out and fan-in z stages (multi_transform_reciprocal_fan_out /
 // fan_in, simple sticks, batch.count members with identical plans; member m's
 // stick array is ZArgs::batch.out[m], its kernel K batch.in[m]). One workgroup

@@ -481,7 +481,35 @@ __device__ __forceinline__ cx<T> row_elem(PairPtr<T, Stream> p) {
   if constexpr (Stream) return cmulc(ld_stream(p.b), ld_stream(p.a));
   else return cmulc(*p.b, *p.a);
 }
-// Src: RowSrc<E> or PairSrc<T, Stream>
+// Packed-real pair row source (x_forward_pair_r2c_kernel): a and b are real
+// arrays read as pairs (s[2m], s[2m+1]), and the element staged is the packed
+// row of their product, a[2m] b[2m] + i a[2m+1] b[2m+1]: a component-wise
+// product, not a complex one (conj is the identity for real fields). Both
+// pointers must be aligned to one pair.
+template <typename T, bool Stream>
+struct PairRealPtr {
+  const cx<T>* a;
+  const cx<T>* b;
+  __device__ __forceinline__ PairRealPtr operator+(long long d) const { return PairRealPtr{a + d, b + d}; }
+};
+template <typename T, bool Stream>
+struct PairRealSrc {
+  PairRealPtr<T, Stream> base;
+  long long stride;
+};
+template <typename T, bool Stream>
+__device__ __forceinline__ cx<T> row_elem(PairRealPtr<T, Stream> p) {
+  cx<T> x, y;
+  if constexpr (Stream) {
+    x = ld_stream(p.a);
+    y = ld_stream(p.b);
+  } else {
+    x = *p.a;
+    y = *p.b;
+  }
+  return mk<T>(x.x * y.x, x.y * y.y);
+}
+// Src: RowSrc<E>, PairSrc<T, Stream> or PairRealSrc<T, Stream>
 template <class Eng, typename T, class Src>
 __device__ __forceinline__ void stage_rows(const Eng& eng, cx<T>* lds, int rows, int len, Src src) {
   if constexpr (!Eng::kBatchedCopy) {
@@ -3240,6 +3268,215 @@ __global__ void __launch_bounds__(Eng::kBlock)
     }
   }
 }
+
+// ------------------------------------- pair operator (Fock) on packed-real rows
+// accumulate_fock of R2C transforms whose half-length h = dimX / 2 has a
+// compile-time engine: a, b and acc are real fields, the pair density a b is
+// formed as packed rows in the forward x stage's row loads, and the accumulating
+// backward x stage updates pairs of acc straight from LDS. The real space domain
+// is neither written nor read. The kernels are built for the engines of
+// R2cFuseFits (x_r2c_fock_fits asks it for both directions' engines): no
+// single-pair kernel of a compile-time engine spilled, so none is excluded.
+
+// Forward x stage of the pair density (R2C, packed-real): x_forward_r2c_kernel
+// whose packed rows are y[m] = a[2m] b[2m] + i a[2m+1] b[2m+1] of two real
+// space-domain arrays (PairRealSrc); the forward half-length FFT and the post
+// pass over the pairs (k, h - k) are that kernel's. StreamAB: the cache policy
+// of the loads of a and b. a may be b: both are only read.
+template <class Eng, typename T, bool StreamAB>
+__device__ __forceinline__ void x_forward_pair_r2c_body(const Eng& eng, const XArgs& a, const T* __restrict__ pa,
+                                                        const T* __restrict__ pb, cx<T>* __restrict__ inter,
+                                                        const cx<T>* __restrict__ twh,
+                                                        const cx<T>* __restrict__ twn) {
+  static_assert(!Eng::kBatchedCopy, "x forward pair r2c: compile-time engines only");
+  SPFFT_LDS_DECL(T);
+  const int B = eng.lines();
+  const int h = eng.n();
+  int tx, ty;
+  block_tile(tx, ty);
+  const int zl = a.zBegin + ty;
+  const int y0 = tx * B;
+  int* xCol = reinterpret_cast<int*>(reinterpret_cast<char*>(lds) + eng.lds_bytes());
+  build_xcol(a, xCol, h + 1);
+  const int yl = min(B, a.Y - y0);
+  const long long off = (static_cast<long long>(zl) * a.Y + y0) * h;  // in pairs
+  const PairRealPtr<T, StreamAB> row0{reinterpret_cast<const cx<T>*>(pa) + off,
+                                      reinterpret_cast<const cx<T>*>(pb) + off};
+  if constexpr (!Eng::kLineFast) {
+    // row-mapped engine: the first pass loads the product rows straight from global memory
+    eng.global_to_lds(lds, twh, [&](int b, int m) -> cx<T> {
+      return b >= yl ? czero<T>() : row_elem<T>(row0 + (static_cast<long long>(b) * h + m));
+    });
+  } else {
+    stage_rows(eng, lds, yl, h, PairRealSrc<T, StreamAB>{row0, h});
+    eng.lds_to_lds(lds, twh);
+  }
+  cx<T>* dst = inter + static_cast<long long>(zl) * a.interZStride + y0;
+  // post pass over the pairs (k, h - k): see x_forward_r2c_kernel
+  for (int idx = threadIdx.x; idx < B * (h / 2 + 1); idx += blockDim.x) {
+    const int b = idx % B, k = idx / B, m = h - k;
+    if (b >= yl) continue;
+    const int ck = xcol_of(a, xCol, k), cm = xcol_of(a, xCol, m);
+    if (ck < 0 && cm < 0) continue;
+    const cx<T> A = lds[eng.out_at(b, k == h ? 0 : k)];
+    const cx<T> Bv = lds[eng.out_at(b, m == h ? 0 : m)];
+    const cx<T> wk = twn[k];
+    if (ck >= 0) {
+      const cx<T> ym = conj(Bv);
+      const cx<T> e = scale(A + ym, T(0.5));
+      const cx<T> o = scale(rot<-1>(A - ym), T(0.5));
+      st_inter(&dst[inter_row(a, ck) + b], e + twm<-1>(o, wk));
+    }
+    if (cm >= 0 && m != k) {
+      const cx<T> ym = conj(A);
+      const cx<T> e = scale(Bv + ym, T(0.5));
+      const cx<T> o = scale(rot<-1>(Bv - ym), T(0.5));
+      st_inter(&dst[inter_row(a, cm) + b], e + twm<-1>(o, mk<T>(-wk.x, wk.y)));
+    }
+  }
+}
+
+template <class Eng, typename T, bool StreamAB>
+__global__ void __launch_bounds__(Eng::kBlock)
+    x_forward_pair_r2c_kernel(Eng eng, XArgs a, const T* __restrict__ pa, const T* __restrict__ pb,
+                              cx<T>* __restrict__ inter, const cx<T>* __restrict__ twh,
+                              const cx<T>* __restrict__ twn) {
+  x_forward_pair_r2c_body<Eng, T, StreamAB>(eng, a, pa, pb, inter, twh, twn);
+}
+
+// Batched launch: blockIdx.z selects the member, whose a is XArgs::batch.in,
+// whose b is second.b (real arrays behind the cx<T> pointers of PairSecond) and
+// whose intermediate is XArgs::batch.out.
+template <class Eng, typename T, bool StreamAB>
+__global__ void __launch_bounds__(Eng::kBlock)
+    x_forward_pair_r2c_batch_kernel(Eng eng, XArgs a, PairSecond<T> second, const cx<T>* __restrict__ twh,
+                                    const cx<T>* __restrict__ twn) {
+  x_forward_pair_r2c_body<Eng, T, StreamAB>(eng, a, static_cast<const T*>(a.batch.in[blockIdx.z]),
+                                            reinterpret_cast<const T*>(second.b[blockIdx.z]),
+                                            static_cast<cx<T>*>(a.batch.out[blockIdx.z]), twh, twn);
+}
+
+// acc pair idx += w * {a.x lds[src(idx)].x, a.y lds[src(idx)].y} for idx in
+// [0, total): fock_rows on packed-real rows (y.x = u[2m], y.y = u[2m+1]), a and
+// acc read and written as pairs, kFockUnroll loads of each in flight. `pa` and
+// `acc` must be aligned to one pair.
+template <bool Stream, typename T, class Src>
+__device__ __forceinline__ void fock_row_pairs(const cx<T>* lds, const cx<T>* __restrict__ pa,
+                                               cx<T>* __restrict__ acc, T w, int total, Src src) {
+  for (int base = threadIdx.x; base < total; base += blockDim.x * kFockUnroll) {
+    cx<T> av[kFockUnroll], r[kFockUnroll];
+#pragma unroll
+    for (int u = 0; u < kFockUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        if constexpr (Stream) {
+          av[u] = ld_stream(pa + idx);
+          r[u] = ld_stream(acc + idx);
+        } else {
+          av[u] = pa[idx];
+          r[u] = acc[idx];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kFockUnroll; ++u) {
+      const int idx = base + u * static_cast<int>(blockDim.x);
+      if (idx < total) {
+        const cx<T> y = lds[src(idx)];
+        const cx<T> o = mk<T>(fma(w * av[u].x, y.x, r[u].x), fma(w * av[u].y, y.y, r[u].y));
+        if constexpr (Stream) st_stream(acc + idx, o);
+        else acc[idx] = o;
+      }
+    }
+  }
+}
+
+// Backward x stage of the pair operator (R2C, packed-real): step (a) of
+// x_apply_r2c_kernel (c2r_rows_to_lds), then acc[2m] += w a[2m] y.x, acc[2m+1]
+// += w a[2m+1] y.y on the workgroup's rows of acc straight from LDS. Tile, LDS
+// layout (lines | Nyquist slot per line | xCol) and grid of the C2R launch. A
+// workgroup owns its rows of acc: no atomics. StreamAcc: cache policy of a and acc.
+template <class Eng, typename T, bool StreamAcc>
+__global__ void __launch_bounds__(Eng::kBlock)
+    x_backward_fock_r2c_kernel(Eng eng, XArgs a, const cx<T>* __restrict__ inter, const T* __restrict__ pa,
+                               T* __restrict__ acc, T w, const cx<T>* __restrict__ twh,
+                               const cx<T>* __restrict__ twn) {
+  static_assert(!Eng::kBatchedCopy, "x backward fock r2c: compile-time engines only");
+  SPFFT_LDS_DECL(T);
+  const int B = eng.lines();
+  const int h = eng.n();
+  int tx, ty;
+  block_tile(tx, ty);
+  const int zl = a.zBegin + ty;
+  const int y0 = tx * B;
+  int* xCol = reinterpret_cast<int*>(reinterpret_cast<cx<T>*>(reinterpret_cast<char*>(lds) + eng.lds_bytes()) + B);
+  build_xcol(a, xCol, h + 1);
+  const int yl = min(B, a.Y - y0);
+  c2r_rows_to_lds(eng, lds, a, xCol, inter + static_cast<long long>(zl) * a.interZStride + y0, yl, twh, twn);
+  const long long off = (static_cast<long long>(zl) * a.Y + y0) * h;  // in pairs
+  fock_row_pairs<StreamAcc>(lds, reinterpret_cast<const cx<T>*>(pa) + off, reinterpret_cast<cx<T>*>(acc) + off, w,
+                            yl * h, [&](int idx) {
+    const int b = idx / h;
+    return eng.out_at(b, idx - b * h);
+  });
+}
+
+// The pairs of a batched launch share acc: the workgroup that owns a tile loops
+// over the members in list order (intermediates from XArgs::batch.in, a and
+// weight from `members`, whose cx<T> pointers hold real arrays), as
+// x_backward_fock_batch_kernel does. The sum order is fixed by the lane's own
+// program order, without atomics; a and acc take the default cache policy
+// because the members revisit the tile.
+template <class Eng, typename T>
+__global__ void __launch_bounds__(Eng::kBlock)
+    x_backward_fock_r2c_batch_kernel(Eng eng, XArgs a, FockMembers<T> members, T* __restrict__ acc,
+                                     const cx<T>* __restrict__ twh, const cx<T>* __restrict__ twn) {
+  static_assert(!Eng::kBatchedCopy, "x backward fock r2c: compile-time engines only");
+  SPFFT_LDS_DECL(T);
+  const int B = eng.lines();
+  const int h = eng.n();
+  int tx, ty;
+  block_tile(tx, ty);
+  const int zl = a.zBegin + ty;
+  const int y0 = tx * B;
+  int* xCol = reinterpret_cast<int*>(reinterpret_cast<cx<T>*>(reinterpret_cast<char*>(lds) + eng.lds_bytes()) + B);
+  build_xcol(a, xCol, h + 1);
+  const int yl = min(B, a.Y - y0);
+  const long long off = (static_cast<long long>(zl) * a.Y + y0) * h;  // in pairs
+  for (int m = 0; m < a.batch.count; ++m) {
+    // the twiddle tables are pinned anew for every member (see x_density_r2c_kernel)
+    const cx<T>* twhM = reinterpret_cast<const cx<T>*>(pin_uniform64(reinterpret_cast<long long>(twh)));
+    const cx<T>* twnM = reinterpret_cast<const cx<T>*>(pin_uniform64(reinterpret_cast<long long>(twn)));
+    if (m > 0) __syncthreads();  // the previous member's rows have been read
+    c2r_rows_to_lds(eng, lds, a, xCol,
+                    static_cast<const cx<T>*>(a.batch.in[m]) + static_cast<long long>(zl) * a.interZStride + y0, yl,
+                    twhM, twnM);
+    fock_row_pairs<false>(lds, members.a[m] + off, reinterpret_cast<cx<T>*>(acc) + off, members.w[m], yl * h,
+                          [&](int idx) {
+      const int b = idx / h;
+      return eng.out_at(b, idx - b * h);
+    });
+  }
+}
+
+// Engines whose batched accumulating packed-real x stage keeps the member loop
+// inside the workgroup (FockBandLoop of the C2C stage); the others run one
+// single-pair launch per member, in order on the stream. The fp32 h = 512 and
+// h = 1024 shapes do not keep it, as for the density (R2cDensityBandLoop): with
+// the loop their kernels took all 256 VGPRs and 84 B and 284 B of scratch per
+// lane (20 and 70 spilled registers).
+template <class Eng>
+struct R2cFockBandLoop {
+  static constexpr bool value = true;
+};
+template <int S, bool LF, bool TwPre>
+struct R2cFockBandLoop<CtEng<float, 512, S, LF, TwPre>> {
+  static constexpr bool value = false;
+};
+template <int S, bool LF, bool TwPre>
+struct R2cFockBandLoop<CtEng<float, 1024, S, LF, TwPre>> {
+  static constexpr bool value = false;
+};
 
 // ------------------------------------------------------------ host helpers
 RtPlan make_rt_plan(int n, std::size_t elemBytes);

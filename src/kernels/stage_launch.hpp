@@ -444,6 +444,121 @@ void launch_x_backward_fock_batch(const XArgs& a, const cx<T>* const* pa, const 
   });
 }
 
+// Pair operator on packed-real rows (R2C, even n, compile-time half-length
+// engines): the forward launch takes the engine, LDS and grid of the R2C launch
+// in launch_x_forward, the accumulating one those of launch_x_density_r2c.
+// x_r2c_fock_fits tells whether both engines of the half-length n / 2 have these
+// kernels (the launchers throw otherwise).
+template <typename T>
+bool x_r2c_fock_fits(int n) {
+  if (!x_r2c_fused_fits<T>(n)) return false;
+  bool fwd = false, bwd = false;
+  with_engine<T, -1, false>(n / 2, [&](auto eng, int, int, std::size_t) { fwd = R2cFuseFits<decltype(eng)>::value; });
+  with_engine<T, +1, true>(n / 2, [&](auto eng, int, int, std::size_t) { bwd = R2cFuseFits<decltype(eng)>::value; });
+  return fwd && bwd;
+}
+
+template <typename T>
+void launch_x_forward_pair_r2c(const XArgs& a, const T* pa, const T* pb, cx<T>* inter, const cx<T>* tw,
+                               const cx<T>* twHalf, hipStream_t stream) {
+  if (a.L <= a.zBegin || a.Y <= 0) return;
+  if (!twHalf || !has_ct_kernel(a.n / 2)) throw InternalError();
+  with_engine<T, -1, false>(a.n / 2, [&](auto eng, int threads, int lines, std::size_t lds) {
+    using E = decltype(eng);
+    if constexpr (R2cFuseFits<E>::value) {
+      auto k = x_forward_pair_r2c_kernel<E, T, SPFFT_FOCK_STREAM != 0>;
+      const std::size_t ldsTotal = lds + std::size_t(a.n / 2 + 1) * sizeof(int) + 16;
+      prepare_kernel(k, ldsTotal);
+      hipLaunchKernelGGL(k, dim3(ceil_div(a.Y, lines), a.L - a.zBegin, 1), dim3(threads), ldsTotal, stream, eng, a,
+                         pa, pb, inter, twHalf, tw);
+      gpu_check_launch("x_forward_pair_r2c", stream);
+    } else {
+      throw InternalError();
+    }
+  });
+}
+
+template <typename T>
+void launch_x_backward_fock_r2c(const XArgs& a, const cx<T>* inter, const T* pa, T* acc, T weight, const cx<T>* tw,
+                                const cx<T>* twHalf, hipStream_t stream) {
+  if (a.L <= a.zBegin || a.Y <= 0) return;
+  if (!twHalf || !has_ct_kernel(a.n / 2)) throw InternalError();
+  with_engine<T, +1, true>(a.n / 2, [&](auto eng, int threads, int lines, std::size_t lds) {
+    using E = decltype(eng);
+    if constexpr (R2cFuseFits<E>::value) {
+      auto k = x_backward_fock_r2c_kernel<E, T, SPFFT_FOCK_STREAM != 0>;
+      const std::size_t ldsTotal =
+          lds + std::size_t(lines) * sizeof(cx<T>) + std::size_t(a.n / 2 + 1) * sizeof(int) + 16;
+      prepare_kernel(k, ldsTotal);
+      hipLaunchKernelGGL(k, dim3(ceil_div(a.Y, lines), a.L - a.zBegin, 1), dim3(threads), ldsTotal, stream, eng, a,
+                         inter, pa, acc, weight, twHalf, tw);
+      gpu_check_launch("x_backward_fock_r2c", stream);
+    } else {
+      throw InternalError();
+    }
+  });
+}
+
+template <typename T>
+void launch_x_forward_pair_r2c_batch(const XArgs& a, const T* const* pb, bool plainLoads, const cx<T>* tw,
+                                     const cx<T>* twHalf, hipStream_t stream) {
+  if (a.L <= a.zBegin || a.Y <= 0 || a.batch.count < 1 || a.batch.count > kMaxBatch) return;
+  if (!twHalf || !has_ct_kernel(a.n / 2)) throw InternalError();
+  PairSecond<T> second{};
+  for (int m = 0; m < a.batch.count; ++m) second.b[m] = reinterpret_cast<const cx<T>*>(pb[m]);
+  with_engine<T, -1, false>(a.n / 2, [&](auto eng, int threads, int lines, std::size_t lds) {
+    using E = decltype(eng);
+    if constexpr (R2cFuseFits<E>::value) {
+      auto k = plainLoads ? x_forward_pair_r2c_batch_kernel<E, T, false> : x_forward_pair_r2c_batch_kernel<E, T, true>;
+      const std::size_t ldsTotal = lds + std::size_t(a.n / 2 + 1) * sizeof(int) + 16;
+      prepare_kernel(k, ldsTotal);
+      hipLaunchKernelGGL(k, dim3(ceil_div(a.Y, lines), a.L - a.zBegin, static_cast<unsigned>(a.batch.count)),
+                         dim3(threads), ldsTotal, stream, eng, a, second, twHalf, tw);
+      gpu_check_launch("x_forward_pair_r2c_batch", stream);
+    } else {
+      throw InternalError();
+    }
+  });
+}
+
+template <typename T>
+void launch_x_backward_fock_r2c_batch(const XArgs& a, const T* const* pa, const T* weights, T* acc,
+                                      const cx<T>* tw, const cx<T>* twHalf, hipStream_t stream) {
+  if (a.L <= a.zBegin || a.Y <= 0 || a.batch.count < 1 || a.batch.count > kMaxBatch) return;
+  if (!twHalf || !has_ct_kernel(a.n / 2)) throw InternalError();
+  FockMembers<T> members{};
+  for (int m = 0; m < a.batch.count; ++m) {
+    members.a[m] = reinterpret_cast<const cx<T>*>(pa[m]);
+    members.w[m] = weights[m];
+  }
+  with_engine<T, +1, true>(a.n / 2, [&](auto eng, int threads, int lines, std::size_t lds) {
+    using E = decltype(eng);
+    if constexpr (R2cFuseFits<E>::value) {
+      const std::size_t ldsTotal =
+          lds + std::size_t(lines) * sizeof(cx<T>) + std::size_t(a.n / 2 + 1) * sizeof(int) + 16;
+      const dim3 grid(ceil_div(a.Y, lines), a.L - a.zBegin, 1);
+      if constexpr (R2cFockBandLoop<E>::value) {
+        auto k = x_backward_fock_r2c_batch_kernel<E, T>;
+        prepare_kernel(k, ldsTotal);
+        hipLaunchKernelGGL(k, grid, dim3(threads), ldsTotal, stream, eng, a, members, acc, twHalf, tw);
+        gpu_check_launch("x_backward_fock_r2c_batch", stream);
+      } else {
+        auto single = x_backward_fock_r2c_kernel<E, T, SPFFT_FOCK_STREAM != 0>;
+        prepare_kernel(single, ldsTotal);
+        XArgs one = a;
+        one.batch.count = 0;
+        for (int m = 0; m < a.batch.count; ++m) {
+          hipLaunchKernelGGL(single, grid, dim3(threads), ldsTotal, stream, eng, one,
+                             static_cast<const cx<T>*>(a.batch.in[m]), pa[m], acc, members.w[m], twHalf, tw);
+          gpu_check_launch("x_backward_fock_r2c", stream);
+        }
+      }
+    } else {
+      throw InternalError();
+    }
+  });
+}
+
 // space[i] = conj(a[i]) * b[i] over `count` elements (complex or, realSpace, real)
 template <typename T>
 void launch_space_pair(void* space, const T* pa, const T* pb, long long count, bool realSpace,

@@ -155,7 +155,8 @@ def _like(rng, ref):
 
 def run_case(cfg, host=False):
     """Runs one drawn configuration. Returns (desc, err, tol, facts); facts holds one dict
-    per rank: fused (the operator's x plan), reciprocal_fused, plan (exchange_plan() of a
+    per rank: fused (the operator's x plan), r2c_fused (fock: the packed-real pair x
+    stages of an R2C plan), reciprocal_fused, plan (exchange_plan() of a
     GPU transform), planes, values."""
     import spfft_amd as sp
     from spfft_amd.parallel import run_ranks
@@ -223,6 +224,8 @@ def run_case(cfg, host=False):
     tol = 2e-4 if (single or (P > 1 and exchange.endswith("FLOAT"))) else 1e-10
     fused_flag = {"local": "apply_local_fused", "density": "density_fused",
                   "reciprocal": "reciprocal_fused", "fock": "fock_fused"}[op]
+    # the pair operator's packed-real x stages on R2C plans have a flag of their own
+    r2c_flag = "fock_r2c_fused" if op == "fock" else None
 
     def arr(x, name):
         """Argument array: numpy on the host engine or for a host pointer, else a GPU tensor."""
@@ -241,12 +244,13 @@ def run_case(cfg, host=False):
 
     def facts_of(t, rank):
         return {"fused": bool(getattr(t, fused_flag)), "reciprocal_fused": bool(t.reciprocal_fused),
+                "r2c_fused": bool(r2c_flag and getattr(t, r2c_flag)),
                 "plan": None if host else t.exchange_plan(), "planes": int(planes[rank]),
                 "values": int(len(parts[rank]))}
 
     def sentinel_of(t):
         """Fills the space domain of a fused x plan with a sentinel; returns its check."""
-        if host or op == "reciprocal" or not getattr(t, fused_flag):
+        if host or op == "reciprocal" or not (getattr(t, fused_flag) or (r2c_flag and getattr(t, r2c_flag))):
             return lambda: True
         space = t.space_domain(PU)
         space.fill_(-7.25)

@@ -21,6 +21,11 @@ ecut) against torch product, apply_reciprocal, torch addcmul_, with the same
 protocol and the modelled bytes of both; with --transforms T > 1 it times T
 pairs of one band per multi_transform_accumulate_fock call against the same T
 pairs as T single accumulate_fock calls into one acc, pairs per second of both;
+with --r2c it times T pairs of real fields into one acc on R2C transforms over the
+hermitian half of the pair sphere, three variants in alternating rounds of one
+process: the torch composition (product, apply_reciprocal, addcmul_), the
+library's composed path (transforms created under SPFFT_R2C_FUSE=0) and the
+fused call, with the stage times of both library variants;
 --op gradient / divergence times PlaneWaveModel's three-component gradient and
 divergence on the density sphere, one multi_transform_reciprocal_fan_out / fan_in
 call against three apply_reciprocal calls with their copies and against the best
@@ -59,7 +64,7 @@ def main():
                     help="FFT grid N^3 instead of the density grid of the cutoff (the cutoff "
                          "sphere may then reach N/2, the transforms' own minimum grid)")
     ap.add_argument("--r2c", action="store_true",
-                    help="--op hartree, local, density, gradient, divergence on R2C transforms "
+                    help="--op hartree, local, density, fock, gradient, divergence on R2C transforms "
                          "(hermitian half of the sphere)")
     a = ap.parse_args()
     import torch
@@ -82,7 +87,9 @@ def main():
         fan(a, basis, model)
         return
     if a.op == "fock":
-        if a.transforms > 1:
+        if a.r2c:
+            fock_r2c(a, basis, model)
+        elif a.transforms > 1:
             fock_multi(a, basis, model)
         else:
             fock(a, basis, model)
@@ -503,6 +510,112 @@ def fock_multi(a, basis, model):
                       "gpu_stage_median_s": stages, "host_scope_median_s": scopes,
                       "model_bytes_per_pair": model_bytes,
                       "model_ratio": model_bytes["single"] / model_bytes["multi"]}), flush=True)
+
+
+def fock_r2c(a, basis, model):
+    """--op fock --r2c: T = --transforms exchange pairs (a_i, b) of real fields into one acc
+    on R2C transforms over the hermitian half of the pair sphere. Variants, alternating in
+    one process (medians and ranges over the rounds): "torch" the composition product into
+    the space domain, apply_reciprocal, addcmul_, pair by pair; "composed" the library's
+    composed path on transforms created under SPFFT_R2C_FUSE=0; "fused" the call on the
+    default plans. Then the GPU stage medians of the single-pair call of each library
+    variant, and the byte model of the x part per pair (G = nx ny nz 8 B, the real grid; I
+    = columns ny nz 16 B, the intermediate): composed 9 G + 2 I (pair pass 3 G, R2C x stage
+    G + I, C2R x stage I + G, accumulating pass 4 G), fused 5 G + 2 I."""
+    import numpy as np
+    import torch
+
+    import spfft_amd as sp
+    nx, ny, nz = basis.fft_dims
+    full, khost = model.exchange_indices, model.exchange_kernel_host
+    keep = (full[:, 0] > 0) | ((full[:, 0] == 0) & ((full[:, 1] > 0) |
+                                                   ((full[:, 1] == 0) & (full[:, 2] >= 0))))
+    idx = np.ascontiguousarray(full[keep])
+    k = torch.as_tensor(np.ascontiguousarray(khost[keep]), device="cuda")
+    T = max(1, a.transforms)
+
+    def make(env):
+        saved = {k_: os.environ.get(k_) for k_ in env}
+        os.environ.update(env)
+        try:
+            ts = []
+            for _ in range(T):
+                grid = sp.Grid(nx, ny, nz, nx * ny, sp.ProcessingUnit.GPU, 1)
+                ts.append(grid.create_transform(sp.ProcessingUnit.GPU, sp.TransformType.R2C,
+                                                nx, ny, nz, nz, idx))
+            return ts
+        finally:
+            for k_, v in saved.items():
+                if v is None:
+                    os.environ.pop(k_, None)
+                else:
+                    os.environ[k_] = v
+
+    fused_ts, composed_ts = make({}), make({"SPFFT_R2C_FUSE": "0"})
+    g = torch.Generator(device="cuda")
+    g.manual_seed(6)
+    shape = (nz, ny, nx)
+    pas = [torch.randn(shape, dtype=torch.float64, device="cuda", generator=g) for _ in range(T)]
+    pb = torch.randn(shape, dtype=torch.float64, device="cuda", generator=g)
+    acc = torch.zeros(shape, dtype=torch.float64, device="cuda")
+    weights = [-1.0 - 0.125 * i for i in range(T)]
+    space = fused_ts[0].space_domain(sp.ProcessingUnit.GPU)
+
+    def call(variant):
+        if variant == "torch":
+            for pa, w in zip(pas, weights):
+                torch.mul(pa, pb, out=space)  # the product written into the space domain
+                u = fused_ts[0].apply_reciprocal(k, scaling=sp.Scaling.FULL)
+                acc.addcmul_(pa, u, value=w)
+            return acc
+        ts = fused_ts if variant == "fused" else composed_ts
+        if T == 1:
+            return ts[0].accumulate_fock(pas[0], pb, k, weights[0], acc, scaling=sp.Scaling.FULL)
+        return sp.multi_transform_accumulate_fock(ts, pas, [pb] * T, k, weights, acc,
+                                                  scaling=sp.Scaling.FULL)
+
+    variants = ("torch", "composed", "fused")
+    rounds, calls = max(3, a.reps), max(2, 10 // T)
+    times = {v: [] for v in variants}
+    for v in variants:
+        call(v)
+    for _ in range(rounds):
+        for v in variants:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                call(v)
+            torch.cuda.synchronize()
+            times[v].append((time.perf_counter() - t0) / calls)
+    med = {v: sorted(x)[len(x) // 2] for v, x in times.items()}
+    stages = {}
+    for v, ts in (("composed", composed_ts), ("fused", fused_ts)):
+        sp.timing_reset()
+        sp.timing_enable(True)
+        try:
+            for _ in range(10):
+                ts[0].accumulate_fock(pas[0], pb, k, weights[0], acc, scaling=sp.Scaling.FULL)
+            ts[0].synchronize()
+            torch.cuda.synchronize()
+            stages[v] = _gpu_stage_medians(sp.timing_json())
+        finally:
+            sp.timing_enable(False)
+    columns = len(set(idx[:, 0].tolist()))
+    inter, real = columns * ny * nz * 16, nx * ny * nz * 8
+    model_x = {"composed": 9 * real + 2 * inter, "fused": 5 * real + 2 * inter}
+    best = min(med["torch"], med["composed"])
+    t = fused_ts[0]
+    print(json.dumps({"workload": "plane-wave exchange pairs", "type": "r2c",
+                      "fft_dims": list(basis.fft_dims), "num_values": int(len(idx)), "columns": columns,
+                      "pairs_per_call": T, "batch": os.environ.get("SPFFT_BATCH", "1"),
+                      "fock_r2c_fused": bool(t.fock_r2c_fused), "reciprocal_fused": bool(t.reciprocal_fused),
+                      "rounds": rounds, "calls_per_round": calls,
+                      "us_per_call": {v: 1e6 * x for v, x in med.items()},
+                      "range_us": {v: [1e6 * min(x), 1e6 * max(x)] for v, x in times.items()},
+                      "ratio_best_other_over_fused": best / med["fused"],
+                      "gpu_stage_median_s": stages,
+                      "model_x_bytes_per_pair": model_x,
+                      "model_x_ratio": model_x["composed"] / model_x["fused"]}), flush=True)
 
 
 def fan(a, basis, model):
